@@ -7,8 +7,14 @@ with the dense (N,N) float32 network, (N,6) state_values and rewards left in HBM
 Workload (BASELINE.json configs[1]): N=1024 agents x 256 envs per GPU, synthetic
 random-init swarms, float32 actions U(-1,1) resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run does what the headline figure needs and no more: set-up, the clock warm-up,
+W warm-up steps, the K timed steps, the outputs of the last timed step written to DIR
+(`--dump-outputs`), and the JSON line. `--full` adds everything else the line can carry
+(below): the CPU baseline, the other forms of config 2 and the other single-GPU configs,
+each of which the `--no-*` options still switch off one by one.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py is its own launcher: the
 parent (which makes no GPU call) checks N against the GPUs it can see, spawns N fresh
@@ -17,7 +23,7 @@ MASTER_PORT set, relays rank 0's JSON line and exits non-zero if any worker fail
 torchrun, WORLD_SIZE must equal --gpus. `--dry-host` runs the same spawn, rendezvous and
 whole-vector reward check with the CPU oracle's rewards and never loads HIP (CPU tests).
 
-At one GPU the same JSON line also carries the other single-GPU configs of
+With --full, at one GPU the same JSON line also carries the other single-GPU configs of
 BASELINE.json as sub-objects: "coverage_config4" (Coverage-v0, R=200, 512 envs) and
 "n8192_config5" (N=8192 x 32 envs), each with ms_per_step, roofline and cpu_baseline;
 plus the step + fused controller, the packed-adjacency output and the Flocking-v0
@@ -111,6 +117,46 @@ def load_traffic(key):
         return None if e is None else float(e["bytes_per_launch"])
     except (OSError, ValueError, KeyError):
         return None
+
+
+DUMP_NETWORK_BYTES = 32 << 20  # --dump-outputs: the network sample's share of the 64 MB
+DUMP_ARRAY_BYTES = 12 << 20    # and the most any other array may take
+
+
+def dump_outputs(env, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as
+    out_dir/<name>.npy: x (B,N,4) float64, state_values (B,N,6) float32 and rewards (B,)
+    float64 whole, and of the dense (B,N,N) float32 network (1 GiB at config 2) a fixed
+    sample, network_sample: whole envs drawn without replacement by RandomState(0), in
+    ascending order, or, where one env's network alone exceeds the sample's share, rows of
+    env 0 drawn the same way. An array over its share is cut to a seeded sample of its
+    leading axis likewise. Returns {name: {"shape", "dtype"[, "sample"]}} for the line."""
+    os.makedirs(out_dir, exist_ok=True)
+    B, N = env.n_envs, env.n_agents
+    rs = np.random.RandomState(0)
+    arrays = {"x": (env.get_state(), None), "state_values": (env.state_values(), None),
+              "rewards": (env.rewards(), None)}
+    per_env = 4 * N * N
+    if per_env <= DUMP_NETWORK_BYTES:
+        envs = np.sort(rs.choice(B, size=min(B, DUMP_NETWORK_BYTES // per_env), replace=False))
+        net = np.stack([np.asarray(env.network(int(b))).reshape(N, N) for b in envs])
+        arrays["network_sample"] = (net, "envs %s of %d" % (envs.tolist(), B))
+    else:
+        rows = np.sort(rs.choice(N, size=max(1, DUMP_NETWORK_BYTES // (4 * N)), replace=False))
+        net = np.asarray(env.network(0)).reshape(N, N)[rows]
+        arrays["network_sample"] = (net, "%d seeded rows of env 0" % len(rows))
+    info = {}
+    for name, (a, sample) in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > DUMP_ARRAY_BYTES and name != "network_sample":
+            keep = np.sort(rs.choice(len(a), size=max(1, DUMP_ARRAY_BYTES * len(a) // a.nbytes), replace=False))
+            a, sample = a[keep], "%d seeded entries of the leading axis" % len(keep)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if sample:
+            info[name]["sample"] = sample
+    return info
 
 
 # ------------------------------------------------------------------ CPU baselines
@@ -975,9 +1021,21 @@ def main():
                     help="skip the configs[3] (Coverage) and configs[4] (N=8192) sub-objects")
     ap.add_argument("--force-dist", action="store_true",
                     help="use the multi-rank path (host channel + RCCL reward all-gather) even at 1 rank")
+    ap.add_argument("--full", action="store_true",
+                    help="flocking workload: also the CPU baseline, the controller, packed-output, host-action "
+                         "and Flocking-v0 lines and, at one GPU, the Coverage, N=8192 and drop-in sub-objects "
+                         "(each still switched off by its --no-* option); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="flocking workload: after the timed steps, write the last step's outputs (x, "
+                         "state_values, rewards, a seeded sample of the network) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if not 1 <= args.metrics_every <= 64:
         ap.error("--metrics-every must be in [1, 64] (the reward ring holds 64 steps)")
+    if args.dump_outputs and (args.workload != "flocking" or args.dry_host):
+        ap.error("--dump-outputs writes the flocking workload's GPU outputs")
+    if not args.full and args.workload == "flocking":
+        args.no_cpu_baseline = args.no_controller_line = args.no_packed_line = True
+        args.no_host_actions_line = args.no_knn_line = args.no_other_configs = True
     if args.cpu_worker is not None:
         return cpu_worker(args.n_agents, args.cpu_worker, args.seed, args.pin_core)
     if args.workload == "coverage":
@@ -1053,6 +1111,9 @@ def main():
     elapsed, kernel_ms = timed(env, ranks, K, plain, per_rank)
 
     extra = {}
+    if args.dump_outputs and rank == 0:
+        # the state after the last timed step (the lines below reset it): rank 0's shard
+        extra["dumped_outputs"] = dump_outputs(env, args.dump_outputs)
     if gather is not None:
         # RCCL's own view of the ranks, checked on rank 0's line: one communicator of
         # world ranks, user ranks 0..world-1, a distinct GPU (PCI bus id) per rank

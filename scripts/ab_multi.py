@@ -23,7 +23,7 @@ res = {name: [] for name, _ in libs}
 for r in range(rounds):
     for name, path in libs:
         env = dict(os.environ, GYMFLOCK_LIB=os.path.abspath(path))
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", os.environ.get("STEPS", "20"),
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", os.environ.get("STEPS", "20"),
                "--warmup", os.environ.get("WARMUP", "5"), "--no-cpu-baseline"] + extra
         p = subprocess.run(cmd, env=env, capture_output=True, timeout=600)
         open(os.path.join(out, "%s_%d.err" % (name, r)), "wb").write(p.stderr)

@@ -1,17 +1,18 @@
 #!/bin/bash
 # One GPU-box session: parity tests, smoke, bench, rocprofv3 kernel trace.
 # Every GPU step has its own time limit; a crash/abort/timeout (exit >= 124) stops the
-# session, ordinary test failures (exit 1) do not.
+# session, ordinary test failures (exit 1) do not. Logs go to $OUT (default: out/).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${OUT:-out}
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 step() {  # step <name> <timeout> <cmd...>
   local name=$1 t=$2; shift 2
   echo "=== $name ($(date +%T))"
-  timeout -k 10 "$t" "$@" > "gpurun_out/$name.log" 2>&1
+  timeout -k 10 "$t" "$@" > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "=== $name rc=$rc"
-  tail -n 25 "gpurun_out/$name.log"
+  tail -n 25 "$OUT/$name.log"
   if [ $rc -ge 124 ] || [ $rc -eq 134 ] || [ $rc -eq 139 ]; then echo "ABORT after $name"; exit $rc; fi
   return 0
 }
@@ -21,9 +22,9 @@ if [ "$MODE" = all ] || [ "$MODE" = test ]; then
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  step bench 600 python bench.py
+  step bench 600 python bench.py --full
 fi
 if [ "$MODE" = all ] || [ "$MODE" = prof ]; then
-  step rocprof_trace 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_trace -o trace -- python bench.py --steps 100 --warmup 10 --no-cpu-baseline
+  step rocprof_trace 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_trace" -o trace -- python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline
 fi
 echo "=== done"
