@@ -120,6 +120,21 @@ struct cov_handle {
   int32_t* lat_grid = nullptr;   // (NI * NJ)
   int lat_L = 0, lat_NI = 0, lat_NJ = 0;
   double lat_key[5] = {0, 0, 0, 0, 0};  // x_min, x_max, y_min, y_max, spacing of `lat`
+  // cov_load_occupancy: the target pool of an occupancy grid, shared by every env
+  cov_occupancy_config occ{};
+  bool pool_loaded = false;
+  int pool_n = 0, pool_n0 = 0, pool_n1 = 0, pool_K = 0;
+  uint8_t* occ_grid = nullptr;      // (n0 * n1)
+  int32_t* pool_cellmap = nullptr;  // (n0 * n1) cell -> pool point or -1
+  int32_t* pool_rawcell = nullptr;  // (kPoolCap) the pool kernel's scratch
+  double2* pool_raw = nullptr;      // (kPoolCap)
+  double2* pool_xy = nullptr;       // (kPoolCap) the pool
+  int32_t* pool_cell = nullptr;     // (kPoolCap) each pool point's cell
+  double* pool_info = nullptr;      // (6) min_xy, max_xy, subgraph_size
+  int32_t* pool_counts = nullptr;   // (3)
+  int32_t* sub_tries = nullptr;     // (B) cov_generate_submaps: tries consumed
+  std::vector<double> pool_host;    // (pool_n, 2)
+  double pool_info_host[6] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -154,7 +169,8 @@ void cov_release(cov_handle* h) {
                   a.receivers, a.obs_step, a.axy, a.nrec, h->err, h->start, h->visited0, h->envsel, h->tm_cost, h->tm_cost8, h->tm_wide, h->tm_prevT, h->tm_glist, h->tm_glen,
                   h->tm_flags, h->needs_random, h->tm_envsel, h->tm_sched, h->tm_lev, h->tm_nslots, h->tm_nlev, h->tm_overflow, h->scratch,
                   h->goff, h->mt_key, h->mt_pos, h->map_key, h->map_pos, h->map_cities, h->map_nraw,
-                  h->map_status, h->lat, h->lat_cell, h->lat_grid};
+                  h->map_status, h->lat, h->lat_cell, h->lat_grid, h->occ_grid, h->pool_cellmap, h->pool_rawcell,
+                  h->pool_raw, h->pool_xy, h->pool_cell, h->pool_info, h->pool_counts, h->sub_tries};
   for (void* p : bufs)
     if (p) hipFree(p);
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
@@ -404,6 +420,18 @@ int ensure_lattice(cov_handle* h, const cov_map_config* mc) {
   return GF_OK;
 }
 
+// The envs' map streams and the map kernels' per-env outputs (allocated on first use).
+int ensure_map_buffers(cov_handle* h) {
+  if (h->map_cities) return GF_OK;
+  const size_t B = h->cfg.n_envs;
+  int rc;
+  if ((rc = calloc_dev(&h->map_key, B * gf::kMtN)) || (rc = calloc_dev(&h->map_pos, B)) ||
+      (rc = calloc_dev(&h->map_cities, B * gf::kMapMaxCities * 2)) || (rc = calloc_dev(&h->map_nraw, B)) ||
+      (rc = calloc_dev(&h->map_status, B)))
+    return rc;
+  return GF_OK;
+}
+
 int put(cov_handle* h, void* dst, const void* src, size_t bytes, bool dev_dst, bool dev_src) {
   if (!dst || !bytes) return GF_OK;
   const hipMemcpyKind k = dev_dst ? (dev_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)
@@ -533,12 +561,7 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
     return cfail(GF_ESTATE, "the envs' map streams were never seeded (COV_MAP_SEED)");
   if (int rc = use(h)) return rc;
   int rc;
-  if (!h->map_cities) {
-    if ((rc = calloc_dev(&h->map_key, (size_t)B * gf::kMtN)) || (rc = calloc_dev(&h->map_pos, (size_t)B)) ||
-        (rc = calloc_dev(&h->map_cities, (size_t)B * gf::kMapMaxCities * 2)) || (rc = calloc_dev(&h->map_nraw, (size_t)B)) ||
-        (rc = calloc_dev(&h->map_status, (size_t)B)))
-      return rc;
-  }
+  if ((rc = ensure_map_buffers(h))) return rc;
   if ((rc = ensure_lattice(h, mc))) return rc;
   // waypoints: the cities plus at most int(dist / road_radius) per Delaunay edge (at most
   // 3 NC - 6 of them, none longer than the cities' square's diagonal), within the LDS left
@@ -647,6 +670,211 @@ int cov_get_targets(cov_handle* h, int env, double* targets) {
   CV_HIP(hipMemcpyAsync(targets, h->tgt + (size_t)env * h->a.Tmax * 2, (size_t)h->ntg_host[env] * 16,
                         hipMemcpyDeviceToHost, h->stream));
   CV_HIP(hipStreamSynchronize(h->stream));
+  return GF_OK;
+}
+
+static_assert(COV_POOL_CAP == gf::kPoolCap && COV_MAP_NO_WINDOW == gf::kMapNoWindow, "gymflock.h and coverage_internal.h disagree");
+
+int cov_load_occupancy(cov_handle* h, const cov_occupancy_config* oc, const uint8_t* grid, int n0, int n1,
+                       int32_t* n_pool_out) {
+  if (!h || !oc || !grid) return cfail(GF_EINVAL, "null argument");
+  if (n0 < 1 || n1 < 1 || (int64_t)n0 * n1 > (1 << 20)) return cfail(GF_EINVAL, "occupancy: grid must be 1 to 2^20 cells");
+  if (oc->downsample_rate < 1) return cfail(GF_EINVAL, "occupancy: downsample_rate must be >= 1");
+  if (!(oc->perimeter_delta >= 0.0) || !std::isfinite(oc->perimeter_delta))
+    return cfail(GF_EINVAL, "occupancy: perimeter_delta must be finite and >= 0");
+  if (!std::isfinite(oc->xyz_min[0]) || !std::isfinite(oc->xyz_min[1])) return cfail(GF_EINVAL, "occupancy: xyz_min must be finite");
+  if (!(oc->num_subgraphs > 0.0) || !std::isfinite(oc->num_subgraphs))
+    return cfail(GF_EINVAL, "occupancy: num_subgraphs must be > 0");
+  if (oc->min_targets < 1 || oc->max_tries < 1) return cfail(GF_EINVAL, "occupancy: min_targets and max_tries must be >= 1");
+  const double res = 0.5 * oc->downsample_rate;
+  const double kd = std::floor(h->cfg.motion_radius / res) + 1.0;
+  if (!(kd <= 16.0)) return cfail(GF_EINVAL, "occupancy: motion_radius spans more than 16 cells of 0.5 * downsample_rate");
+  // an upper bound of the pool before any launch: free cells with an occupied cell within
+  // floor(perimeter_delta) cells on both axes (the kernel applies the Euclidean test)
+  const int KP = (int)std::min<double>(std::floor(oc->perimeter_delta), (double)std::max(n0, n1));
+  std::vector<int32_t> sum((size_t)(n0 + 1) * (n1 + 1), 0);  // occupied cells, summed-area table
+  for (int i = 0; i < n0; ++i)
+    for (int j = 0; j < n1; ++j)
+      sum[(size_t)(i + 1) * (n1 + 1) + j + 1] = (grid[(size_t)i * n1 + j] ? 1 : 0) + sum[(size_t)i * (n1 + 1) + j + 1] +
+                                                sum[(size_t)(i + 1) * (n1 + 1) + j] - sum[(size_t)i * (n1 + 1) + j];
+  if (sum.back() == 0) return cfail(GF_EINVAL, "occupancy: the grid has no occupied cell (from_occupancy's minimum is empty)");
+  int64_t bound = 0;
+  for (int i = 0; i < n0; ++i)
+    for (int j = 0; j < n1; ++j) {
+      if (grid[(size_t)i * n1 + j]) continue;
+      const int i0 = std::max(i - KP, 0), i1 = std::min(i + KP + 1, n0), j0 = std::max(j - KP, 0), j1 = std::min(j + KP + 1, n1);
+      const int occ = sum[(size_t)i1 * (n1 + 1) + j1] - sum[(size_t)i0 * (n1 + 1) + j1] - sum[(size_t)i1 * (n1 + 1) + j0] +
+                      sum[(size_t)i0 * (n1 + 1) + j0];
+      bound += occ > 0 ? 1 : 0;
+    }
+  if (bound > gf::kPoolCap)
+    return cfail(GF_EINVAL, "occupancy: the grid may give " + std::to_string(bound) + " targets, more than the pool holds (" +
+                                std::to_string(gf::kPoolCap) + ")");
+  if (int rc = use(h)) return rc;
+  int rc;
+  if (!h->pool_xy) {
+    if ((rc = calloc_dev(&h->pool_rawcell, (size_t)gf::kPoolCap)) || (rc = calloc_dev(&h->pool_raw, (size_t)gf::kPoolCap)) ||
+        (rc = calloc_dev(&h->pool_cell, (size_t)gf::kPoolCap)) || (rc = calloc_dev(&h->pool_info, (size_t)6)) ||
+        (rc = calloc_dev(&h->pool_counts, (size_t)3)) || (rc = calloc_dev(&h->sub_tries, (size_t)h->cfg.n_envs)) ||
+        (rc = calloc_dev(&h->pool_xy, (size_t)gf::kPoolCap)))
+      return rc;
+  }
+  h->pool_loaded = false;
+  for (void* p : {static_cast<void*>(h->occ_grid), static_cast<void*>(h->pool_cellmap)})
+    if (p) CV_HIP(hipFree(p));
+  h->occ_grid = nullptr;
+  h->pool_cellmap = nullptr;
+  if ((rc = calloc_dev(&h->occ_grid, (size_t)n0 * n1)) || (rc = calloc_dev(&h->pool_cellmap, (size_t)n0 * n1))) return rc;
+  CV_HIP(hipMemcpyAsync(h->occ_grid, grid, (size_t)n0 * n1, hipMemcpyHostToDevice, h->stream));
+  gf::CovPoolArgs p{};
+  p.n0 = n0;
+  p.n1 = n1;
+  p.grid = h->occ_grid;
+  p.KP = KP;
+  p.perimeter_delta = oc->perimeter_delta;
+  p.res = res;
+  p.xmin0 = oc->xyz_min[0];
+  p.xmin1 = oc->xyz_min[1];
+  p.check_connected = oc->check_connected ? 1 : 0;
+  p.link_radius = h->cfg.motion_radius;
+  p.K = (int)kd;
+  p.num_subgraphs = oc->num_subgraphs;
+  p.cell = h->pool_cellmap;
+  p.raw_cell = h->pool_rawcell;
+  p.raw = h->pool_raw;
+  p.pool = h->pool_xy;
+  p.pool_cell = h->pool_cell;
+  p.info = h->pool_info;
+  p.counts = h->pool_counts;
+  hipError_t e = gf::launch_cov_pool(p, h->stream);
+  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_pool_kernel: ") + hipGetErrorString(e));
+  int32_t counts[3] = {0, 0, 0};
+  CV_HIP(hipMemcpyAsync(counts, h->pool_counts, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
+  CV_HIP(hipMemcpyAsync(h->pool_info_host, h->pool_info, sizeof(h->pool_info_host), hipMemcpyDeviceToHost, h->stream));
+  CV_HIP(hipStreamSynchronize(h->stream));
+  if (counts[2] || counts[1] > gf::kPoolCap) return cfail(GF_EINVAL, "occupancy: more targets than the pool holds");
+  if (counts[1] < 1) return cfail(GF_EINVAL, "occupancy: no free cell within perimeter_delta of an occupied one");
+  h->pool_host.assign((size_t)counts[1] * 2, 0.0);
+  CV_HIP(hipMemcpy(h->pool_host.data(), h->pool_xy, (size_t)counts[1] * 16, hipMemcpyDeviceToHost));
+  h->occ = *oc;
+  h->pool_n = counts[1];
+  h->pool_n0 = n0;
+  h->pool_n1 = n1;
+  h->pool_K = (int)kd;
+  h->pool_loaded = true;
+  if (n_pool_out) *n_pool_out = counts[1];
+  return GF_OK;
+}
+
+int cov_get_pool(cov_handle* h, double* targets, double* min_xy, double* max_xy, double* subgraph_size) {
+  if (!h) return cfail(GF_EINVAL, "null handle");
+  if (!h->pool_loaded) return cfail(GF_ESTATE, "no target pool (cov_load_occupancy)");
+  if (targets) std::memcpy(targets, h->pool_host.data(), h->pool_host.size() * sizeof(double));
+  if (min_xy) std::memcpy(min_xy, h->pool_info_host, 16);
+  if (max_xy) std::memcpy(max_xy, h->pool_info_host + 2, 16);
+  if (subgraph_size) std::memcpy(subgraph_size, h->pool_info_host + 4, 16);
+  return GF_OK;
+}
+
+int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double* draws, int n_draws, int flags,
+                         int32_t* n_targets_out, int32_t* status_out, int32_t* tries_out) {
+  if (!h) return cfail(GF_EINVAL, "null handle");
+  if (flags & ~(COV_MAP_SEED | COV_MAP_DRAWS)) return cfail(GF_EINVAL, "flags: COV_MAP_SEED | COV_MAP_DRAWS");
+  const bool given = flags & COV_MAP_DRAWS;
+  if (given && !draws) return cfail(GF_EINVAL, "COV_MAP_DRAWS needs the draws");
+  if (given && n_draws < 1) return cfail(GF_EINVAL, "COV_MAP_DRAWS needs n_draws >= 1");
+  if (given && n_draws > (1 << 20)) return cfail(GF_EINVAL, "n_draws too large");
+  const int B = h->cfg.n_envs;
+  if (env >= B) return cfail(GF_EINVAL, "env index out of range");
+  if (!h->pool_loaded) return cfail(GF_ESTATE, "no target pool (cov_load_occupancy)");
+  if (!(h->occ.num_subgraphs > 1.0))
+    return cfail(GF_EINVAL, "num_subgraphs <= 1 is not sampled: the map is the whole pool (cov_set_targets)");
+  if (!given && (flags & COV_MAP_SEED) && map_seed + (uint64_t)B > 0x100000000ull)
+    return cfail(GF_EINVAL, "map_seed + n_envs must fit in 32 bits (np.random.seed)");
+  if (!given && !(flags & COV_MAP_SEED) && !h->map_seeded)
+    return cfail(GF_ESTATE, "the envs' map streams were never seeded (COV_MAP_SEED)");
+  if (gf::cov_submap_lds_bytes(h->pool_n) > 150 * 1024) return cfail(GF_EINVAL, "the pool is too large for the sampler's LDS");
+  if (int rc = use(h)) return rc;
+  if (int rc = ensure_map_buffers(h)) return rc;
+  const int b0 = env < 0 ? 0 : env, b1 = env < 0 ? B : env + 1, nsel = b1 - b0;
+  std::vector<int32_t> sel;
+  for (int b = b0; b < b1; ++b) sel.push_back(b);
+  CV_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, h->stream));
+  const double* info = h->pool_info_host;
+  gf::CovSubmapArgs m{};
+  m.n_sel = nsel;
+  m.envs = h->envsel;
+  m.R = h->a.R;
+  m.Tmax = h->a.Tmax;
+  m.P = h->pool_n;
+  m.pool = h->pool_xy;
+  m.pool_cell = h->pool_cell;
+  m.cell = h->pool_cellmap;
+  m.n0 = h->pool_n0;
+  m.n1 = h->pool_n1;
+  m.K = h->pool_K;
+  m.link_radius = h->cfg.motion_radius;
+  // np.random.uniform(low=min_xy, high=max_xy - subgraph_size): low + (high - low) * u
+  m.lo_x = info[0];
+  m.lo_y = info[1];
+  m.range_x = (info[2] - info[4]) - info[0];
+  m.range_y = (info[3] - info[5]) - info[1];
+  m.sub_x = info[4];
+  m.sub_y = info[5];
+  m.min_targets = h->occ.min_targets;
+  m.max_tries = h->occ.max_tries;
+  m.n_draws = given ? n_draws : 0;
+  m.mt_key = h->map_key;
+  m.mt_pos = h->map_pos;
+  m.seed0 = static_cast<uint32_t>(map_seed);
+  m.seed = (flags & COV_MAP_SEED) ? 1 : 0;
+  m.tgt = h->tgt;
+  m.ntg = h->ntg;
+  m.nraw = h->map_nraw;
+  m.status = h->map_status;
+  m.tries = h->sub_tries;
+  if (given) {
+    unsigned char* d = nullptr;
+    const size_t bytes = (size_t)nsel * n_draws * 16;
+    if (int rc = scratch(h, bytes, &d)) return rc;
+    CV_HIP(hipMemcpyAsync(d, draws, bytes, hipMemcpyHostToDevice, h->stream));
+    m.draws = reinterpret_cast<const double*>(d);
+  } else if (flags & COV_MAP_SEED) {
+    h->map_seeded = true;
+  }
+  hipError_t e = gf::launch_cov_submap(m, h->stream);
+  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_submap_kernel: ") + hipGetErrorString(e));
+  e = gf::launch_cov_graph(h->a, h->envsel, nsel, h->stream);
+  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
+  std::vector<int32_t> nraw(nsel), st(nsel), tr(nsel), ntg(B);
+  CV_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  CV_HIP(hipMemcpyAsync(st.data(), h->map_status + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  CV_HIP(hipMemcpyAsync(tr.data(), h->sub_tries + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  CV_HIP(hipMemcpyAsync(ntg.data(), h->ntg, B * 4, hipMemcpyDeviceToHost, h->stream));
+  if (int rc2 = check_err(h)) return rc2;  // synchronises; motion-graph errors (degree > 4, edges)
+  CV_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::string bad;
+  for (int k = 0; k < nsel; ++k) {
+    const int b = b0 + k;
+    h->ntg_host[b] = ntg[b];
+    h->tm_valid[b] = 0;
+    if (n_targets_out) n_targets_out[k] = nraw[k];
+    if (status_out) status_out[k] = st[k];
+    if (tries_out) tries_out[k] = tr[k];
+    if (!bad.empty()) continue;
+    if (st[k] & gf::kMapTooMany)
+      bad = "env " + std::to_string(b) + ": the map has " + std::to_string(nraw[k]) +
+            " targets, more than max_nodes - n_robots = " + std::to_string(h->a.Tmax);
+    else if (st[k] & gf::kMapTooFew)
+      bad = "env " + std::to_string(b) + ": the map has " + std::to_string(nraw[k]) + " targets, fewer than the robots";
+    else if ((st[k] & gf::kMapNoWindow) && !given)
+      bad = "env " + std::to_string(b) + ": no window with a component of " + std::to_string(h->occ.min_targets) +
+            " targets in max_tries = " + std::to_string(h->occ.max_tries) + " tries";
+  }
+  h->tm_ready = false;
+  h->has_graph = true;
+  for (int b = 0; b < B; ++b) h->has_graph = h->has_graph && h->ntg_host[b] > 0;
+  if (!bad.empty()) return cfail(GF_EINVAL, "cov_generate_submaps: " + bad);
   return GF_OK;
 }
 
@@ -1304,3 +1532,10 @@ int cov_sync(cov_handle* h) {
 }
 
 }  // extern "C"
+
+// coverage_arl.hip is a source of its own in this directory's Makefile (GF_ARL_OWN_TU). A
+// build that lists the library's sources without it (the host-sanitizer build of the
+// C-ABI, tests/asan) gets its kernels and launchers here, with this file's flags.
+#ifndef GF_ARL_OWN_TU
+#include "coverage_arl.hip"
+#endif

@@ -233,6 +233,91 @@ __device__ __forceinline__ void mt_regen(uint32_t* k) {
   __syncthreads();
 }
 
+// Shared by the map kernels (coverage_maps.hip, coverage_arl.hip): workgroup compaction
+// and the largest connected component of a radius graph by union-find in LDS.
+//
+// Exclusive scan of one int per thread over a workgroup of NT threads; *total = the sum.
+// wsum: LDS of NT / 64 + 1 ints. Every thread calls it.
+template <int NT>
+__device__ __forceinline__ int block_exscan(int v, int* wsum, int* total) {
+  constexpr int NW = NT / 64;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+  if (lane == 63) wsum[w] = x;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int k = 0; k < NW; ++k) {
+      const int t = wsum[k];
+      wsum[k] = run;
+      run += t;
+    }
+    wsum[NW] = run;
+  }
+  __syncthreads();
+  const int r = wsum[w] + x - v;
+  *total = wsum[NW];
+  __syncthreads();
+  return r;
+}
+
+__device__ __forceinline__ int uf_find(volatile int32_t* p, int x) {
+  for (int y = p[x]; y != x; y = p[x]) x = y;
+  return x;
+}
+
+// Joins the trees of a and b: the larger root is hooked under the smaller, so a parent
+// is always a lower index and each tree's root is its lowest node.
+__device__ __forceinline__ void uf_unite(int32_t* p, int a, int b) {
+  for (;;) {
+    a = uf_find(p, a);
+    b = uf_find(p, b);
+    if (a == b) return;
+    if (a > b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    if (atomicCAS(&p[b], b, a) == b) return;
+  }
+}
+
+// After every uf_unite (and a barrier): points each of the n nodes at its root, counts
+// the components (cnt, zeroed by the caller) and returns the largest as size << 32 |
+// (0xFFFFFFFF - root): ties go to the lowest root, argmax(bincount(labels))'s first-label
+// rule (scipy numbers components in order of their lowest node). best_s: one LDS word
+// zeroed by the caller before its last barrier. Every thread of the NT calls it.
+template <int NT>
+__device__ __forceinline__ unsigned long long uf_largest(int32_t* parent, int32_t* cnt, int n,
+                                                         unsigned long long* best_s) {
+  const int tid = threadIdx.x;
+  for (int u = tid; u < n; u += NT) {
+    const int r = uf_find(parent, u);
+    parent[u] = r;
+    atomicAdd(&cnt[r], 1);
+  }
+  __syncthreads();
+  unsigned long long key = 0ull;
+  for (int u = tid; u < n; u += NT)
+    if (parent[u] == u) {
+      const unsigned long long k2 = (static_cast<unsigned long long>(cnt[u]) << 32) | (0xFFFFFFFFull - u);
+      key = k2 > key ? k2 : key;
+    }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(key, d, 64);
+    key = o > key ? o : key;
+  }
+  if ((tid & 63) == 0) atomicMax(best_s, key);
+  __syncthreads();
+  return *best_s;
+}
+
 // Greedy expert (coverage_expert.hip).
 struct CovTmArgs {
   int R, M, Tmax, horizon;
@@ -332,6 +417,60 @@ constexpr int32_t kMapNearDegenerate = 1, kMapTooMany = 2, kMapTooFew = 4, kMapO
 size_t cov_map_lds_bytes(int L, int wcap, int G);
 hipError_t launch_cov_map_cities(const CovMapArgs& a, hipStream_t s);
 hipError_t launch_cov_map(const CovMapArgs& a, hipStream_t s);
+
+// CoverageARL-v0 / CoverageFull-v0 (coverage_arl.hip): the target pool of an occupancy
+// grid (make_map.py:234-271, coverage_arl.py:46-62), shared by every env of a handle, and
+// the per-reset subgraph sampler (coverage_arl.py:64-83).
+constexpr int kPoolCap = 4096;  // pool points before the component step (grid_slice10: 1714)
+struct CovPoolArgs {
+  int n0, n1;                // grid (n0, n1) bytes, nonzero = occupied
+  const uint8_t* grid;
+  int KP;                    // floor(perimeter_delta): cells searched either side for an occupied cell
+  double perimeter_delta;
+  double res;                // 0.5 * downsample_rate
+  double xmin0, xmin1;       // xyz_min
+  int check_connected;
+  double link_radius;        // motion_radius
+  int K;                     // cells searched either side for a link
+  double num_subgraphs;
+  int32_t* cell;             // (n0 * n1) cell j * n0 + i -> pool point or -1 (out)
+  int32_t* raw_cell;         // (kPoolCap) scratch: cell of each point before the component step
+  double2* raw;              // (kPoolCap) scratch: those points
+  double2* pool;             // (kPoolCap) out: the pool (all_targets), cell order
+  int32_t* pool_cell;        // (kPoolCap) out: each pool point's cell
+  double* info;              // (6) out: min_xy, max_xy, subgraph_size
+  int32_t* counts;           // (3) out: points before the component step, pool points, overflow flag
+};
+struct CovSubmapArgs {
+  int n_sel;
+  const int32_t* envs;       // (n_sel) env of each workgroup
+  int R, Tmax;
+  int P;                     // pool points
+  const double2* pool;       // (P)
+  const int32_t* pool_cell;  // (P)
+  const int32_t* cell;       // (n0 * n1)
+  int n0, n1, K;
+  double link_radius;
+  double lo_x, lo_y;         // graph_start = lo + range * u (np.random.uniform(low, high))
+  double range_x, range_y;
+  double sub_x, sub_y;       // subgraph_size: graph_end = graph_start + subgraph_size
+  int min_targets, max_tries;
+  const double* draws;       // (n_sel, n_draws, 2) given graph_start values, or nullptr: the streams
+  int n_draws;
+  uint32_t* mt_key;          // (B, 624) each env's map stream (cov_generate_maps' streams)
+  int32_t* mt_pos;           // (B)
+  uint32_t seed0;
+  int seed;
+  double* tgt;               // (B, Tmax, 2) out: the accepted component's points, pool order
+  int32_t* ntg;              // (B) out: targets (0 when no map was accepted or it is refused)
+  int32_t* nraw;             // (B) out: the accepted component's size
+  int32_t* status;           // (B) out: kMapTooMany | kMapTooFew | kMapNoWindow
+  int32_t* tries;            // (B) out: tries consumed
+};
+constexpr int32_t kMapNoWindow = 16;
+size_t cov_submap_lds_bytes(int P);
+hipError_t launch_cov_pool(const CovPoolArgs& a, hipStream_t s);
+hipError_t launch_cov_submap(const CovSubmapArgs& a, hipStream_t s);
 
 size_t cov_step_lds_bytes(int R, int M);
 // Observation wire formats: the flat FlattenDictWrapper rows (B, 15M+1) and the

@@ -40,55 +40,6 @@ constexpr double kEps = 1.1102230246251565e-16;  // 2^-53
 constexpr double kIccBound = 4.0 * (10.0 + 96.0 * kEps) * kEps;
 constexpr double kCcwBound = 4.0 * (3.0 + 16.0 * kEps) * kEps;
 
-// Exclusive scan of one int per thread over the workgroup; *total = the sum. wsum: LDS
-// of kMapWaves + 1 ints. Every thread calls it.
-__device__ int block_exscan(int v, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int k = 0; k < kMapWaves; ++k) {
-      const int t = wsum[k];
-      wsum[k] = run;
-      run += t;
-    }
-    wsum[kMapWaves] = run;
-  }
-  __syncthreads();
-  const int r = wsum[w] + x - v;
-  *total = wsum[kMapWaves];
-  __syncthreads();
-  return r;
-}
-
-__device__ __forceinline__ int uf_find(volatile int32_t* p, int x) {
-  for (int y = p[x]; y != x; y = p[x]) x = y;
-  return x;
-}
-
-// Joins the trees of a and b: the larger root is hooked under the smaller, so a parent
-// is always a lower index and each tree's root is its lowest node.
-__device__ __forceinline__ void uf_unite(int32_t* p, int a, int b) {
-  for (;;) {
-    a = uf_find(p, a);
-    b = uf_find(p, b);
-    if (a == b) return;
-    if (a > b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    if (atomicCAS(&p[b], b, a) == b) return;
-  }
-}
-
 // make_map.py:208 for env b: 2 * NC doubles of np.random.uniform from the env's stream
 // (numpy's legacy random_sample: (a >> 5) * 2^26 + (b >> 6), over 2^53; then lo + range
 // * u). One wave per env; every lane runs the draw chain, lane 0 writes.
@@ -277,7 +228,7 @@ __global__ __launch_bounds__(kMapThreads) void cov_map_kernel(CovMapArgs a) {
     int run = 0;
     for (int c = c0; c < c1; ++c) run += cend[c];
     int wtot;
-    run = block_exscan(run, wsum, &wtot);
+    run = block_exscan<kMapThreads>(run, wsum, &wtot);
     for (int c = c0; c < c1; ++c) {  // each cell's start; the scatter below leaves its end
       const int n = cend[c];
       cend[c] = run;
@@ -313,7 +264,7 @@ __global__ __launch_bounds__(kMapThreads) void cov_map_kernel(CovMapArgs a) {
   int local = 0;
   for (int l = l0; l < l1; ++l) local += cidx[l];
   int t0;
-  int pos = block_exscan(local, wsum, &t0);
+  int pos = block_exscan<kMapThreads>(local, wsum, &t0);
   for (int l = l0; l < l1; ++l) {
     if (cidx[l]) {
       parent[pos] = pos;
@@ -349,28 +300,8 @@ __global__ __launch_bounds__(kMapThreads) void cov_map_kernel(CovMapArgs a) {
     }
   }
   __syncthreads();
-  // 5c. every node to its root, component sizes
-  for (int u = tid; u < t0; u += kMapThreads) {
-    const int r = uf_find(parent, u);
-    parent[u] = r;
-    atomicAdd(&cnt[r], 1);
-  }
-  __syncthreads();
-  // 5d. the largest component, ties to the lowest root
-  unsigned long long key = 0ull;
-  for (int u = tid; u < t0; u += kMapThreads)
-    if (parent[u] == u) {
-      const unsigned long long k2 = (static_cast<unsigned long long>(cnt[u]) << 32) | (0xFFFFFFFFull - u);
-      key = k2 > key ? k2 : key;
-    }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long o = __shfl_xor(key, d, 64);
-    key = o > key ? o : key;
-  }
-  if ((tid & 63) == 0) atomicMax(&best_s, key);
-  __syncthreads();
-  const unsigned long long best = best_s;
+  // 5c, 5d. every node to its root, component sizes; the largest, ties to the lowest root
+  const unsigned long long best = uf_largest<kMapThreads>(parent, cnt, t0, &best_s);
   const int T = static_cast<int>(best >> 32);
   const int root = static_cast<int>(0xFFFFFFFFull - (best & 0xFFFFFFFFull));
   int fl = flags_s;
@@ -388,7 +319,7 @@ __global__ __launch_bounds__(kMapThreads) void cov_map_kernel(CovMapArgs a) {
   local = 0;
   for (int l = l0; l < l1; ++l) local += (cidx[l] >= 0 && parent[cidx[l]] == root) ? 1 : 0;
   int tot;
-  pos = block_exscan(local, wsum, &tot);
+  pos = block_exscan<kMapThreads>(local, wsum, &tot);
   double2* out = reinterpret_cast<double2*>(a.tgt) + (size_t)b * a.Tmax;
   for (int l = l0; l < l1; ++l)
     if (cidx[l] >= 0 && parent[cidx[l]] == root) out[pos++] = a.lat[l];

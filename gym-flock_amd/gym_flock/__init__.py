@@ -18,6 +18,9 @@ ENV_IDS = {
     "FlockingObstacle-v0": ("gym_flock.envs.flocking:FlockingObstacleEnv", 200),    # :72-76
     "FlockingStochastic-v0": ("gym_flock.envs.flocking:FlockingStochasticEnv", 500),  # :84-88
     "FlockingTwoFlocks-v0": ("gym_flock.envs.flocking:FlockingTwoFlocksEnv", 500),  # :90-94
+    "CoverageFull-v0": ("gym_flock.envs.spatial:CoverageFullEnv", 100000),          # :21-25
+    "CoverageARL-v1": ("gym_flock.envs.spatial:CoverageARLEnv", 100000),            # :27-31
+    "CoverageARL-v0": ("gym_flock.envs.spatial:CoverageARLEnv", 100000),            # :34-38
 }
 
 if HAVE_GYM:  # pragma: no cover - gym is not installed in the build image

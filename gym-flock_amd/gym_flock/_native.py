@@ -87,8 +87,28 @@ def map_lattice(mc=None):
     return out
 
 
+class CovOccupancyConfig(ctypes.Structure):
+    _fields_ = [("downsample_rate", ctypes.c_int32), ("perimeter_delta", ctypes.c_double),
+                ("xyz_min", ctypes.c_double * 2), ("check_connected", ctypes.c_int32),
+                ("num_subgraphs", ctypes.c_double), ("min_targets", ctypes.c_int32),
+                ("max_tries", ctypes.c_int32)]
+
+
+XYZ_MIN = (-321.0539855957031, -276.5395050048828)  # make_map.py:264
+
+
+def occupancy_config(downsample_rate=10, perimeter_delta=2.0, check_connected=True, num_subgraphs=3.0,
+                     min_targets=200, max_tries=4096, xyz_min=XYZ_MIN):
+    """The reference's occupancy-map parameters (coverage_arl.py:17-19, MIN_GRAPH_SIZE :10,
+    make_map.py:264-265); max_tries bounds the sampler's retry loop on the device streams."""
+    return CovOccupancyConfig(int(downsample_rate), float(perimeter_delta), (ctypes.c_double * 2)(*xyz_min),
+                              int(bool(check_connected)), float(num_subgraphs), int(min_targets), int(max_tries))
+
+
 COV_MAP_SEED = 0x1
 COV_MAP_CITIES = 0x2
+COV_MAP_DRAWS = 0x4
+COV_MAP_NO_WINDOW = 0x10
 COV_MAP_NEAR_DEGENERATE = 0x1
 COV_MAP_TOO_MANY = 0x2
 COV_MAP_TOO_FEW = 0x4
@@ -170,6 +190,9 @@ SIGNATURES = {
     "cov_set_targets": [_P, _I, _I, _P],
     "cov_generate_maps": [_P, _P, _I, ctypes.c_uint64, _P, _I, _P, _P, _P],
     "cov_get_targets": [_P, _I, _P],
+    "cov_load_occupancy": [_P, _P, _P, _I, _I, _P],
+    "cov_get_pool": [_P, _P, _P, _P, _P],
+    "cov_generate_submaps": [_P, _I, ctypes.c_uint64, _P, _I, _I, _P, _P, _P],
     "cov_map_lattice": [_P, _P, _P],
     "cov_reset": [_P, _P, _P],
     "cov_reset_seeded": [_P, ctypes.c_uint64, ctypes.c_double, _P, _P],
@@ -807,6 +830,53 @@ class CoverageHandle:
             err.n_targets, err.status = n, st  # which envs' maps were refused, and why
             raise err
         return (n, st, co) if fetch else None
+
+    def load_occupancy(self, grid, config=None):
+        """The target pool of an occupancy grid ((n0, n1), nonzero = occupied) on the device
+        (cov_load_occupancy; make_map.py:234-271, coverage_arl.py:46-62), shared by every
+        env of the handle. Returns the pool's size."""
+        g = np.ascontiguousarray(np.asarray(grid) != 0, dtype=np.uint8)
+        assert g.ndim == 2, g.shape
+        self.occ = config or occupancy_config()
+        n = ctypes.c_int32(0)
+        check(self.lib.cov_load_occupancy(self.h, ctypes.byref(self.occ), ptr(g), g.shape[0], g.shape[1],
+                                          ctypes.byref(n)))
+        self.n_pool = n.value
+        return n.value
+
+    def pool(self):
+        """(all_targets (n_pool, 2), min_xy (1, 2), max_xy (1, 2), subgraph_size (1, 2)) of the
+        loaded pool (cov_get_pool)."""
+        t = np.empty((self.n_pool, 2), np.float64)
+        lo, hi, sub = (np.empty((1, 2), np.float64) for _ in range(3))
+        check(self.lib.cov_get_pool(self.h, ptr(t), ptr(lo), ptr(hi), ptr(sub)))
+        return t, lo, hi, sub
+
+    def generate_submaps(self, map_seed=None, draws=None, env=-1):
+        """A new sampled map (cov_generate_submaps, coverage_arl.py:64-83) for env `env`
+        (-1: every env), then its motion graph. draws=None: each env's map stream, seeded
+        np.random.seed(map_seed + b) when map_seed is given, else continued; draws (n_sel,
+        K, 2): the graph_start values of K tries. Returns (n_targets, status, tries) per
+        selected env; a refused map raises GymFlockError carrying the same three."""
+        nsel = self.n_envs if env < 0 else 1
+        flags, d, k = 0, None, 0
+        if draws is not None:
+            d = np.ascontiguousarray(draws, dtype=np.float64)
+            k = d.size // (2 * nsel)
+            d = d.reshape(nsel, k, 2)
+            flags |= COV_MAP_DRAWS
+        elif map_seed is not None:
+            flags |= COV_MAP_SEED
+        n = np.full(nsel, -1, np.int32)
+        st = np.zeros(nsel, np.int32)
+        tr = np.zeros(nsel, np.int32)
+        rc = self.lib.cov_generate_submaps(self.h, int(env), int(map_seed or 0), ptr(d), k, flags, ptr(n), ptr(st),
+                                           ptr(tr))
+        if rc:
+            err = GymFlockError(rc, self.lib.fe_last_error().decode(errors="replace"))
+            err.n_targets, err.status, err.tries = n, st, tr
+            raise err
+        return n, st, tr
 
     def targets(self, env, n_targets):
         """The (n_targets, 2) targets of env `env`'s current map (n_targets: its size, as

@@ -11,7 +11,8 @@ the target map (global np.random, maps.generate_targets) and reset()'s start and
 unvisited draws (self.np_random), in the reference's call order.
 
 Supported configuration: the module constants the reference ships with (PAD_ACTIONS,
-COLLISION_CHECKS, PAD_NODES, distance edge features, HIDE_NODES False). Like the
+COLLISION_CHECKS, PAD_NODES, distance edge features, HIDE_NODES False; pad_nodes=False only
+for an env whose maps all have the same node count, CoverageFull-v0). Like the
 reference, observations alias buffers that the next step overwrites only in the sense
 that each call returns fresh host copies of the device arrays.
 """
@@ -50,9 +51,13 @@ class CoverageEnv(Env):
                  nearby_starts=NEARBY_STARTS, horizon=HORIZON, hide_nodes=False,
                  n_node_feat=N_NODE_FEAT, device=0):
         super(CoverageEnv, self).__init__()
-        if hide_nodes or not pad_nodes or n_node_feat != N_NODE_FEAT:
-            raise NotImplementedError("only the reference's shipped configuration (PAD_NODES, no hidden nodes, "
+        if hide_nodes or n_node_feat != N_NODE_FEAT:
+            raise NotImplementedError("only the reference's shipped configuration (no hidden nodes, "
                                       "3 node features) is implemented")
+        if not pad_nodes and not self._fixed_node_count():
+            # max_nodes = n_agents (coverage.py:540-541) sizes the device arrays: the node count
+            # has to be known before the handle is made, and must not change with the map
+            raise NotImplementedError("pad_nodes=False needs a map whose node count is fixed (CoverageFull-v0)")
         self.keys = ['nodes', 'edges', 'senders', 'receivers', 'step']
         self.n_node_feat = n_node_feat
         self.hide_nodes = hide_nodes
@@ -76,8 +81,8 @@ class CoverageEnv(Env):
         self.obs_radius = self.res * 1.2
         self.n_actions = N_ACTIONS
         self.device = device
-        self._h = nat.CoverageHandle(n_robots, 1, max_nodes, episode_length, res, self.motion_radius, device,
-                                     horizon=horizon)
+        self._h = None
+        self._make_handle()
         self._map_cfg = nat.map_config_default(self.motion_radius, xmax, ymax, N_CITIES, DELTA)
         self.map_status = 0  # cov_generate_maps status bits of the current map
         if init_graph:
@@ -107,6 +112,17 @@ class CoverageEnv(Env):
     def seed(self, seed=None):
         self.np_random, seed = np_random(seed)
         return [seed]
+
+    def _fixed_node_count(self):
+        """Whether every map of this env has the same node count (pad_nodes=False)."""
+        return False
+
+    def _make_handle(self):
+        """The device handle for self.max_nodes padded nodes (again when max_nodes changes)."""
+        if self._h is not None:
+            self._h.close()
+        self._h = nat.CoverageHandle(self.n_robots, 1, self.max_nodes, self.episode_length, self.res,
+                                     self.motion_radius, self.device, horizon=self.horizon)
 
     # --------------------------------------------------------------- graph setup
     def _generate_targets(self):
@@ -187,6 +203,11 @@ class CoverageEnv(Env):
         targets, graph_changed = self._generate_targets()
         if graph_changed:
             self._initialize_graph(targets, on_device=True)
+        elif self.nearby_starts:  # :398-402: the same graph, a new start region
+            n_nearest = self.get_n_nearest(self.np_random.choice(self.n_targets), self.n_robots * NEARBY_DENSITY)
+            region = np.zeros(self.n_targets, bool)
+            region[list(n_nearest)] = True
+            self.start_region = region.tolist()
         starts = self.np_random.choice(np.arange(self.n_targets)[self.start_region], size=(self.n_robots,),
                                        replace=False)
         unvisited = np.arange(self.n_targets)[self.unvisited_region] + self.n_robots
@@ -222,7 +243,9 @@ class CoverageEnv(Env):
         if self._abuf is None:
             self._abuf = np.empty((1, R), np.int32)
         self._abuf[0] = a
-        ng = self._want_greedy
+        # the fused next-greedy reads the per-node greedy lists, built for at most 1024 targets
+        # (COV_NEXT_GREEDY); larger maps take controller()'s cov_controller_greedy row scan
+        ng = self._want_greedy and self._h.t_max <= 1024
         lay = self._layout
         if lay is None or lay[0] != ng:
             a64 = lambda b: (b + 63) & ~63  # noqa: E731

@@ -139,6 +139,11 @@ class VecCoverage:
     Each env gets its own target graph (set_targets(env=b)) or all share one
     (env=-1); reset() draws starts and the unvisited set per env from
     np.random.RandomState(seed + env_offset + b) in the reference's order.
+
+    CoverageARL-v0 batches: VecCoverage(B, 4, max_nodes=1000, episode_length=50, res=5.0),
+    then load_occupancy(grid); reset(new_maps=True) then samples every env's map from the
+    pool (generate_submaps). The batched reset keeps uniform starts (cov_reset_seeded):
+    the reference's nearby_starts region is drawn by the drop-in CoverageARLEnv only.
     """
 
     def __init__(self, n_envs, n_robots, max_nodes=1000, episode_length=75, res=5.5,
@@ -150,6 +155,37 @@ class VecCoverage:
         self.n_targets = np.zeros(self.n_envs, np.int64)
         self._rngs = None          # host-held np_random streams (else on the device)
         self._dev_streams = False  # the device holds every env's np_random stream
+        self._pool = False         # an occupancy pool is loaded: new maps are sampled from it
+
+    def load_occupancy(self, grid, downsample_rate=10, perimeter_delta=2.0, check_connected=True, num_subgraphs=3.0,
+                       min_targets=200, max_tries=4096):
+        """The target pool of an occupancy grid, shared by every env (cov_load_occupancy;
+        coverage_arl.py:46-62). Returns the pool's size. With num_subgraphs <= 1 every
+        env's map is the whole pool, set here."""
+        cfg = nat.occupancy_config(downsample_rate, perimeter_delta, check_connected, num_subgraphs, min_targets,
+                                   max_tries)
+        n = self.h.load_occupancy(grid, cfg)
+        self._pool = True
+        self._sampled = num_subgraphs > 1
+        if not self._sampled:
+            self.set_targets(self.h.pool()[0])
+        return n
+
+    def generate_submaps(self, map_seed=None):
+        """A new sampled map for every env (coverage_arl.py:64-83, cov_generate_submaps):
+        env b's window draws come from its own map stream, seeded np.random.seed(map_seed +
+        env_offset + b) when map_seed is given, else continued from its previous map.
+        Returns (n_targets (B,), status (B,), tries (B,)). With num_subgraphs <= 1 nothing
+        is drawn: the maps stay the pool."""
+        if not self._pool:
+            raise nat.GymFlockError(nat.GF_ESTATE, "load_occupancy first")
+        if not self._sampled:
+            z = np.zeros(self.n_envs, np.int32)
+            return self.n_targets.astype(np.int32), z, z.copy()
+        seed = None if map_seed is None else int(map_seed) + self.env_offset
+        n, st, tries = self.h.generate_submaps(map_seed=seed)
+        self.n_targets[:] = n
+        return n, st, tries
 
     def set_targets(self, targets, env=-1):
         self.h.set_targets(targets, env)
@@ -180,9 +216,12 @@ class VecCoverage:
         draws="device" (cov_reset_seeded): the draws run on the device, one wave per env;
         "host": RandomState loops here (~0.5 ms per env), then cov_reset and cov_set_rng.
         Both return (start (B,R) target-local, visited (B, max_nodes-R)), bit-identical.
-        new_maps: each env first draws a new map on the device (generate_maps(map_seed)),
-        as every reference reset() does (:378-397)."""
-        if new_maps:
+        new_maps: each env first draws a new map on the device (generate_maps(map_seed), or
+        generate_submaps(map_seed) once an occupancy pool is loaded), as every reference
+        reset() does (:378-397)."""
+        if new_maps and self._pool:
+            self.generate_submaps(map_seed)
+        elif new_maps:
             self.generate_maps(map_seed)
         self._rngs = None
         if draws == "device":

@@ -370,6 +370,52 @@ int cov_get_targets(cov_handle* h, int env, double* targets);
  * the capacity is short, which fails with GF_EINVAL). xy may be NULL to query *n. */
 int cov_map_lattice(const cov_map_config* mc, double* xy, int32_t* n);
 
+/* ----- CoverageARL-v0 / CoverageFull-v0 (gym_flock/envs/spatial/coverage_arl.py) -----
+ * The targets come from an occupancy grid (make_map.from_occupancy, make_map.py:234-271):
+ * free cells within perimeter_delta cells of an occupied one, as points ((cell * res) +
+ * xyz_min) + res / 2 with res = 0.5 * downsample_rate, rotated (x, y) = (t_y, -t_x), and
+ * with check_connected the largest component of their radius graph (load_graph,
+ * coverage_arl.py:46-62; the handle's motion_radius). That pool is shared by every env of
+ * the handle. With num_subgraphs > 1 every reset() samples a random window of
+ * (max_xy - min_xy) / num_subgraphs of it and keeps the window's largest component,
+ * until one holds min_targets points (_generate_targets, coverage_arl.py:64-83). */
+typedef struct cov_occupancy_config {
+  int32_t downsample_rate;   /* 10 (the reference's grid_slice10 map)                     */
+  double perimeter_delta;    /* 2.0, in cells                                             */
+  double xyz_min[2];         /* (-321.0539855957031, -276.5395050048828) (make_map.py:264) */
+  int32_t check_connected;   /* keep the pool's largest component (coverage_arl.py:49-54)  */
+  double num_subgraphs;      /* 3.0; <= 1: no sampling, the map is the whole pool          */
+  int32_t min_targets;       /* MIN_GRAPH_SIZE = 200 (coverage_arl.py:10)                  */
+  int32_t max_tries;         /* bound of the sampler's retry loop on the streams (4096);
+                                the reference's loop is unbounded                          */
+} cov_occupancy_config;
+#define COV_MAP_DRAWS     0x4  /* cov_generate_submaps: the graph_start draws are given     */
+#define COV_MAP_NO_WINDOW 0x10 /* status bit: no try gave a component of min_targets points */
+#define COV_POOL_CAP      4096 /* pool points before the component step                     */
+/* The target pool of grid (n0, n1) bytes, nonzero = occupied, on the device (one launch).
+ * *n_pool_out (may be NULL) receives the pool's size. GF_EINVAL, before any launch, for a
+ * grid without an occupied cell or one that may give more than COV_POOL_CAP points. */
+int cov_load_occupancy(cov_handle* h, const cov_occupancy_config* cfg, const uint8_t* grid, int n0, int n1,
+                       int32_t* n_pool_out);
+/* The pool (n_pool, 2) in cell order (all_targets), min_xy[2], max_xy[2] and
+ * subgraph_size[2] = (max_xy - min_xy) / num_subgraphs; any may be NULL. Host copies. */
+int cov_get_pool(cov_handle* h, double* targets, double* min_xy, double* max_xy, double* subgraph_size);
+/* A new sampled map for env `env` (env < 0: every env), then its motion graph and static
+ * observation as cov_set_targets builds them. The draws graph_start = low + (high - low) *
+ * u (low = min_xy, high = max_xy - subgraph_size; x, then y: two doubles per try) come
+ * from each env's map stream (the streams of cov_generate_maps; COV_MAP_SEED seeds env
+ * b's as np.random.seed(map_seed + b) first), at most max_tries tries; or with
+ * COV_MAP_DRAWS from draws (n_sel, n_draws, 2), the graph_start values themselves (what
+ * np.random.uniform(low, high, size=(n_draws, 1, 2)) returns), at most n_draws tries.
+ * n_targets_out, status_out, tries_out (n_sel; may be NULL): the accepted component's size,
+ * the status bits, the tries consumed. On the streams an env left without a window
+ * (COV_MAP_NO_WINDOW) fails the call with GF_EINVAL like TOO_MANY / TOO_FEW (judged on the
+ * accepted component), that env left without a graph; with COV_MAP_DRAWS a list that gave
+ * no window is reported in status_out only (the caller draws again). GF_ESTATE without a
+ * pool, GF_EINVAL with num_subgraphs <= 1 (the map is the pool: cov_set_targets). */
+int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double* draws, int n_draws, int flags,
+                         int32_t* n_targets_out, int32_t* status_out, int32_t* tries_out);
+
 /* reset() after its random draws (:405-424): start[B][R] target-local start nodes,
  * visited[B][max_nodes-R] (1 = visited); computes reset's observation (:424). */
 int cov_reset(cov_handle* h, const int32_t* start, const uint8_t* visited);
