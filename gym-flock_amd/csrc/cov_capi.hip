@@ -135,6 +135,15 @@ struct cov_handle {
   int32_t* sub_tries = nullptr;     // (B) cov_generate_submaps: tries consumed
   std::vector<double> pool_host;    // (pool_n, 2)
   double pool_info_host[6] = {0, 0, 0, 0, 0, 0};
+  // cov_set_hidden: the hidden-node observation (coverage_hidden.hip), rewritten by
+  // cov_hidden_kernel after every pass that makes an observation
+  bool hidden = false;
+  uint8_t* discovered = nullptr;  // (B,M)
+  float* hnodes = nullptr;        // (B,M,4)
+  int32_t* hsenders = nullptr;    // (B,4M)
+  uint8_t* gmask = nullptr;       // (B,Tmax) visited | !discovered
+  int32_t* ngmask = nullptr;      // (B)
+  int32_t* hnkeep = nullptr;      // (B) hsenders slots that are not -1
 };
 
 namespace {
@@ -170,7 +179,8 @@ void cov_release(cov_handle* h) {
                   h->tm_flags, h->needs_random, h->tm_envsel, h->tm_sched, h->tm_lev, h->tm_nslots, h->tm_nlev, h->tm_overflow, h->scratch,
                   h->goff, h->mt_key, h->mt_pos, h->map_key, h->map_pos, h->map_cities, h->map_nraw,
                   h->map_status, h->lat, h->lat_cell, h->lat_grid, h->occ_grid, h->pool_cellmap, h->pool_rawcell,
-                  h->pool_raw, h->pool_xy, h->pool_cell, h->pool_info, h->pool_counts, h->sub_tries};
+                  h->pool_raw, h->pool_xy, h->pool_cell, h->pool_info, h->pool_counts, h->sub_tries,
+                  h->discovered, h->hnodes, h->hsenders, h->gmask, h->ngmask, h->hnkeep};
   for (void* p : bufs)
     if (p) hipFree(p);
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
@@ -315,6 +325,55 @@ int ensure_time_matrix(cov_handle* h) {
   return GF_OK;
 }
 
+// 4 * DELTA (coverage.py:335): the module constant, whatever the env's res
+constexpr double kHiddenRadius = 4.0 * 5.5;
+constexpr const char* kHiddenFused =
+    "a handle with hidden nodes has no fused expert (the step kernel reads the visited flags, not the expert's "
+    "visited-or-undiscovered mask): take the actions from cov_controller_greedy, then cov_step";
+
+gf::CovHiddenArgs hidden_args(const cov_handle* h) {
+  gf::CovHiddenArgs g{};
+  const gf::CovArgs& a = h->a;
+  g.B = h->cfg.n_envs;
+  g.R = a.R;
+  g.M = a.M;
+  g.Tmax = a.Tmax;
+  g.radius = kHiddenRadius;
+  g.ntg = h->ntg;
+  g.tgt = h->tgt;
+  g.xr = a.xr;
+  g.visited = a.visited;
+  g.nodes = a.nodes;
+  g.senders = a.senders;
+  g.receivers = a.receivers;
+  g.n_motion = a.n_motion;
+  g.discovered = h->discovered;
+  g.hnodes = h->hnodes;
+  g.hsenders = h->hsenders;
+  g.gmask = h->gmask;
+  g.ngmask = h->ngmask;
+  g.nkeep = h->hnkeep;
+  return g;
+}
+
+// Hidden handles: discovered := robots only for the n envs listed on the device (nullptr:
+// every env), on the handle's stream.
+int hidden_reset(cov_handle* h, const int32_t* envs, int n) {
+  if (!h->hidden) return GF_OK;
+  hipError_t e = gf::launch_cov_hidden_reset(hidden_args(h), envs, n, h->stream);
+  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_hidden_reset_kernel: ") + hipGetErrorString(e));
+  return GF_OK;
+}
+
+// Hidden handles: the hidden observation of every env from the ordinary one, on the
+// handle's stream (which the caller has ordered behind the pass that made it).
+int hidden_pass(cov_handle* h) {
+  if (!h->hidden) return GF_OK;
+  hipError_t e = gf::launch_cov_hidden(hidden_args(h), h->stream);
+  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_hidden_kernel: ") + hipGetErrorString(e));
+  return GF_OK;
+}
+
 // Device scratch of at least `bytes` (grown on demand, reused across calls).
 int scratch(cov_handle* h, size_t bytes, unsigned char** out) {
   if (bytes > h->scratch_bytes) {
@@ -330,14 +389,29 @@ int scratch(cov_handle* h, size_t bytes, unsigned char** out) {
 }
 
 // Edge counts of the unpack_obs tuple and their exclusive offsets.
-void graph_sizes(const cov_handle* h, bool mask_all, std::vector<int32_t>& ne, std::vector<int64_t>& off) {
+// keep: a hidden handle's kept slots per env (hnkeep), which replace the motion + action
+// edge count.
+void graph_sizes(const cov_handle* h, bool mask_all, const int32_t* keep, std::vector<int32_t>& ne,
+                 std::vector<int64_t>& off) {
   const int B = h->cfg.n_envs, R = h->cfg.n_robots, M = h->cfg.max_nodes;
   ne.assign(B, 0);
   off.assign(B + 1, 0);
   for (int b = 0; b < B; ++b) {
-    ne[b] = (mask_all || b == 0) ? h->n_motion_host[b] + 8 * R : 4 * M;
+    ne[b] = (mask_all || b == 0) ? (keep ? keep[b] : h->n_motion_host[b] + 8 * R) : 4 * M;
     off[b + 1] = off[b] + ne[b];
   }
+}
+
+// A hidden handle's kept slots per env, read from the device (synchronises); empty otherwise.
+int hidden_keep(cov_handle* h, std::vector<int32_t>& keep) {
+  keep.clear();
+  if (!h->hidden) return GF_OK;
+  if (!h->has_state) return cfail(GF_ESTATE, "hidden nodes: reset first (the edge counts follow the observation)");
+  if (int rc = use(h)) return rc;
+  keep.resize(h->cfg.n_envs);
+  CV_HIP(hipMemcpyAsync(keep.data(), h->hnkeep, keep.size() * 4, hipMemcpyDeviceToHost, h->stream));
+  CV_HIP(hipStreamSynchronize(h->stream));
+  return GF_OK;
 }
 
 // Python's float floor division (numpy floor_divide on float64), for generate_lattice's
@@ -522,6 +596,7 @@ int cov_set_targets(cov_handle* h, int env, int n_targets, const double* targets
   CV_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   hipError_t e = gf::launch_cov_graph(h->a, h->envsel, (int)sel.size(), h->stream);
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
+  if (int rc = hidden_reset(h, h->envsel, (int)sel.size())) return rc;
   if (int rc = check_err(h)) return rc;
   CV_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
   for (int b = b0; b < b1; ++b) h->tm_valid[b] = 0;
@@ -629,6 +704,7 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_map_kernel: ") + hipGetErrorString(e));
   e = gf::launch_cov_graph(h->a, h->envsel, nsel, h->stream);
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
+  if (int rc3 = hidden_reset(h, h->envsel, nsel)) return rc3;
   std::vector<int32_t> nraw(nsel), st(nsel), ntg(B);
   CV_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
   CV_HIP(hipMemcpyAsync(st.data(), h->map_status + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
@@ -846,6 +922,7 @@ int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_submap_kernel: ") + hipGetErrorString(e));
   e = gf::launch_cov_graph(h->a, h->envsel, nsel, h->stream);
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
+  if (int rc3 = hidden_reset(h, h->envsel, nsel)) return rc3;
   std::vector<int32_t> nraw(nsel), st(nsel), tr(nsel), ntg(B);
   CV_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
   CV_HIP(hipMemcpyAsync(st.data(), h->map_status + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
@@ -890,10 +967,12 @@ int cov_reset(cov_handle* h, const int32_t* start, const uint8_t* visited) {
   CV_HIP(hipMemcpyAsync(h->visited0, visited, B * Tm, hipMemcpyHostToDevice, h->stream));
   hipError_t e = gf::launch_cov_reset(h->a, h->start, h->visited0, h->stream);
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_reset_kernel: ") + hipGetErrorString(e));
+  if (int rc = hidden_reset(h, nullptr, (int)B)) return rc;
   gf::CovArgs a = h->a;
   a.actions = nullptr;
   e = gf::launch_cov_step(a, h->stream);
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
+  if (int rc = hidden_pass(h)) return rc;
   CV_HIP(hipStreamSynchronize(h->stream));
   h->has_state = true;
   return GF_OK;
@@ -918,10 +997,12 @@ int cov_reset_seeded(cov_handle* h, uint64_t seed, double frac_active, int32_t* 
   hipError_t e = gf::launch_cov_seed_reset(a, static_cast<uint32_t>(seed), frac_active, h->start, h->visited0, h->stream);
   if (e == hipSuccess) e = gf::launch_cov_reset(h->a, h->start, h->visited0, h->stream);
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_reset_seeded: ") + hipGetErrorString(e));
+  if (int rc = hidden_reset(h, nullptr, (int)B)) return rc;
   a = h->a;
   a.actions = nullptr;
   e = gf::launch_cov_step(a, h->stream);
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
+  if (int rc = hidden_pass(h)) return rc;
   if (start_out) CV_HIP(hipMemcpyAsync(start_out, h->start, B * R * 4, hipMemcpyDeviceToHost, h->stream));
   if (visited_out) CV_HIP(hipMemcpyAsync(visited_out, h->visited0, B * Tm, hipMemcpyDeviceToHost, h->stream));
   CV_HIP(hipStreamSynchronize(h->stream));
@@ -973,6 +1054,7 @@ int cov_step_expert(cov_handle* h, int n_steps, double* rewards, uint8_t* done) 
   if (!h) return cfail(GF_EINVAL, "null handle");
   if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
   if (n_steps < 1) return cfail(GF_EINVAL, "n_steps must be at least 1");
+  if (h->hidden) return cfail(GF_EINVAL, std::string("cov_step_expert: ") + kHiddenFused);
   if (!h->mt_key) return cfail(GF_ESTATE, "set the envs' np_random streams first (cov_set_rng or cov_reset_seeded)");
   if (h->cfg.n_robots > gf::kMtN) return cfail(GF_EINVAL, "n_robots <= 624 (one key regeneration per step)");
   if (int rc = use(h)) return rc;
@@ -1015,6 +1097,7 @@ int cov_step(cov_handle* h, const int32_t* actions, int flags) {
   if (!h) return cfail(GF_EINVAL, "null handle");
   if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
   CV_HIP(hipSetDevice(h->cfg.device));
+  if ((flags & COV_ACTIONS_GREEDY) && h->hidden) return cfail(GF_EINVAL, std::string("COV_ACTIONS_GREEDY: ") + kHiddenFused);
   gf::CovArgs a = h->a;
   if ((flags & COV_GREEDY_RNG) && !(flags & COV_ACTIONS_GREEDY))
     return cfail(GF_EINVAL, "COV_GREEDY_RNG needs COV_ACTIONS_GREEDY");
@@ -1078,6 +1161,11 @@ int cov_step(cov_handle* h, const int32_t* actions, int flags) {
     if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
     h->s2_pending = true;
     if (h->timing) h->tw_steps++;
+    if (h->hidden) {  // one pass over every env on `stream`, behind both halves and ahead of the next ones
+      if (int rc = join_s2(h)) return rc;
+      if (int rc = hidden_pass(h)) return rc;
+      h->main_dirty = true;
+    }
     if (!(flags & (COV_ACTIONS_DEVICE | COV_ACTIONS_RESIDENT | COV_ACTIONS_GREEDY)))
       CV_HIP(hipStreamSynchronize(h->stream));
     return GF_OK;
@@ -1098,6 +1186,7 @@ int cov_step(cov_handle* h, const int32_t* actions, int flags) {
   }
   hipError_t e = gf::launch_cov_step(a, h->stream);
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
+  if (int rc = hidden_pass(h)) return rc;  // inside the sampled window: the step a hidden handle pays for
   if (sample) {
     CV_HIP(hipEventRecord(h->ev[h->ev_used + 1], h->stream));
     h->ev_used += 2;
@@ -1132,6 +1221,7 @@ int cov_step_host(cov_handle* h, const int32_t* actions, float* nodes, float* ed
   if (!h || !actions) return cfail(GF_EINVAL, "null argument");
   if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
   if (flags & ~COV_NEXT_GREEDY) return cfail(GF_EINVAL, "flags: 0 or COV_NEXT_GREEDY");
+  if (h->hidden) return cfail(GF_EINVAL, std::string("cov_step_host: ") + kHiddenFused);
   const bool ng = flags & COV_NEXT_GREEDY;
   if (!ng && (next_actions || needs_random)) return cfail(GF_EINVAL, "next_actions / needs_random need COV_NEXT_GREEDY");
   const size_t B = h->cfg.n_envs, R = h->cfg.n_robots, M = h->cfg.max_nodes, E = 4 * M, n = B * R;
@@ -1365,8 +1455,10 @@ int cov_controller_greedy(cov_handle* h, int32_t* actions, uint8_t* needs_random
   g.cost8 = h->tm_cost8;
   g.wide = h->tm_wide;
   g.prevT = h->tm_prevT;
-  g.visited = a.visited;
-  g.nvisited = a.nvisited;
+  // hidden nodes: controller()'s second mask (coverage.py:819-820) joins the first, and with
+  // it the column-0 quirk: any_vis is true when any target is visited or undiscovered
+  g.visited = h->hidden ? h->gmask : a.visited;
+  g.nvisited = h->hidden ? h->ngmask : a.nvisited;
   g.nbr = a.nbr;
   g.cnt = a.cnt;
   g.actions = h->actions;
@@ -1436,14 +1528,20 @@ int cov_get_flat_obs(cov_handle* h, void* dst, int flags) {
   if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
   if (int rc = use(h)) return rc;
   const bool f32 = flags & COV_FLAT_F32;
-  const size_t bytes = (size_t)h->cfg.n_envs * (15 * (size_t)h->cfg.max_nodes + 1) * (f32 ? 4 : 8);
+  const int nf = h->hidden ? 4 : 3;
+  const size_t bytes = (size_t)h->cfg.n_envs * ((size_t)(12 + nf) * h->cfg.max_nodes + 1) * (f32 ? 4 : 8);
   void* out = dst;
   if (!(flags & COV_OUT_DEVICE)) {
     unsigned char* sc = nullptr;
     if (int rc = scratch(h, bytes, &sc)) return rc;
     out = sc;
   }
-  hipError_t e = gf::launch_cov_flat_obs(h->a, out, f32, h->stream);
+  gf::CovArgs fa = h->a;
+  if (h->hidden) {
+    fa.nodes = h->hnodes;
+    fa.senders = h->hsenders;
+  }
+  hipError_t e = gf::launch_cov_flat_obs(fa, nf, out, f32, h->stream);
   if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_flat_obs_kernel: ") + hipGetErrorString(e));
   if (flags & COV_OUT_DEVICE) return GF_OK;  // stream-ordered; cov_sync before reading
   CV_HIP(hipMemcpyAsync(dst, out, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -1454,9 +1552,10 @@ int cov_get_flat_obs(cov_handle* h, void* dst, int flags) {
 int cov_graphs_tuple_sizes(cov_handle* h, int32_t* n_edge, int64_t* total_edges, int flags) {
   if (!h) return cfail(GF_EINVAL, "null handle");
   if (!h->has_graph) return cfail(GF_ESTATE, "set the target graph first (cov_set_targets)");
-  std::vector<int32_t> ne;
+  std::vector<int32_t> ne, keep;
   std::vector<int64_t> off;
-  graph_sizes(h, flags & COV_MASK_ALL, ne, off);
+  if (int rc = hidden_keep(h, keep)) return rc;
+  graph_sizes(h, flags & COV_MASK_ALL, h->hidden ? keep.data() : nullptr, ne, off);
   if (n_edge) std::memcpy(n_edge, ne.data(), ne.size() * sizeof(int32_t));
   if (total_edges) *total_edges = off.back();
   return GF_OK;
@@ -1471,9 +1570,10 @@ int cov_get_graphs_tuple(cov_handle* h, int32_t* n_node, float* nodes, int32_t* 
   if (int rc = use(h)) return rc;
   const bool dev = flags & COV_OUT_DEVICE;
   const int B = h->cfg.n_envs, M = h->cfg.max_nodes;
-  std::vector<int32_t> ne;
+  std::vector<int32_t> ne, keep;
   std::vector<int64_t> off;
-  graph_sizes(h, flags & COV_MASK_ALL, ne, off);
+  if (int rc = hidden_keep(h, keep)) return rc;
+  graph_sizes(h, flags & COV_MASK_ALL, h->hidden ? keep.data() : nullptr, ne, off);
   const int64_t total = off.back();
   if (!h->goff)
     if (hipMalloc(reinterpret_cast<void**>(&h->goff), (B + 1) * sizeof(int64_t)) != hipSuccess)
@@ -1489,7 +1589,9 @@ int cov_get_graphs_tuple(cov_handle* h, int32_t* n_node, float* nodes, int32_t* 
       s_out = reinterpret_cast<int32_t*>(sc + (size_t)total * 4);
       r_out = reinterpret_cast<int32_t*>(sc + (size_t)total * 8);
     }
-    hipError_t e = gf::launch_cov_graphs(h->a, h->goff, flags & COV_MASK_ALL, e_out, s_out, r_out, h->stream);
+    hipError_t e = h->hidden ? gf::launch_cov_hidden_graphs(hidden_args(h), h->a.edges, h->goff, flags & COV_MASK_ALL,
+                                                            e_out, s_out, r_out, h->stream)
+                             : gf::launch_cov_graphs(h->a, h->goff, flags & COV_MASK_ALL, e_out, s_out, r_out, h->stream);
     if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_graphs_kernel: ") + hipGetErrorString(e));
     if (!dev) {
       if (int rc = put(h, edges, e_out, (size_t)total * 4, false, true)) return rc;
@@ -1497,7 +1599,8 @@ int cov_get_graphs_tuple(cov_handle* h, int32_t* n_node, float* nodes, int32_t* 
       if (int rc = put(h, receivers, r_out, (size_t)total * 4, false, true)) return rc;
     }
   }
-  if (int rc = put(h, nodes, h->a.nodes, (size_t)B * M * 3 * sizeof(float), dev, true)) return rc;
+  if (int rc = put(h, nodes, h->hidden ? h->hnodes : h->a.nodes, (size_t)B * M * (h->hidden ? 4 : 3) * sizeof(float), dev, true))
+    return rc;
   std::vector<int32_t> nn(B, M);
   if (int rc = put(h, n_node, nn.data(), B * sizeof(int32_t), dev, false)) return rc;
   if (int rc = put(h, n_edge, ne.data(), B * sizeof(int32_t), dev, false)) return rc;
@@ -1520,6 +1623,46 @@ int cov_set_streams(cov_handle* h, int n) {
   return GF_OK;
 }
 
+int cov_set_hidden(cov_handle* h, int enable) {
+  if (!h) return cfail(GF_EINVAL, "null handle");
+  if (enable != 0 && enable != 1) return cfail(GF_EINVAL, "enable must be 0 or 1");
+  if (int rc = use(h)) return rc;
+  if (!enable) {
+    h->hidden = false;
+    return GF_OK;
+  }
+  const size_t B = h->cfg.n_envs, M = h->cfg.max_nodes, Tm = h->a.Tmax;
+  if (gf::cov_hidden_lds_bytes(h->cfg.n_robots, h->cfg.max_nodes) > 64 * 1024)
+    return cfail(GF_EINVAL, "hidden nodes: n_robots * 16 + max_nodes / 4 bytes exceed the pass's 64 KB of LDS");
+  if (!h->discovered) {
+    int rc;
+    if ((rc = calloc_dev(&h->discovered, B * M)) || (rc = calloc_dev(&h->hnodes, B * M * 4)) ||
+        (rc = calloc_dev(&h->hsenders, B * 4 * M)) || (rc = calloc_dev(&h->gmask, B * Tm)) ||
+        (rc = calloc_dev(&h->ngmask, B)) || (rc = calloc_dev(&h->hnkeep, B)))
+      return rc;
+  }
+  h->hidden = true;
+  if (int rc = hidden_reset(h, nullptr, (int)B)) return rc;
+  // an observation taken before this call gets its hidden form at once
+  if (h->has_state)
+    if (int rc = hidden_pass(h)) return rc;
+  CV_HIP(hipStreamSynchronize(h->stream));
+  return GF_OK;
+}
+
+int cov_get_hidden_obs(cov_handle* h, int env, float* nodes4, int32_t* senders, uint8_t* discovered) {
+  if (!h || env < 0 || env >= h->cfg.n_envs) return cfail(GF_EINVAL, "bad argument");
+  if (!h->hidden) return cfail(GF_ESTATE, "the handle does not hide nodes (cov_set_hidden)");
+  if ((nodes4 || senders) && !h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
+  if (int rc = use(h)) return rc;
+  const size_t M = h->cfg.max_nodes;
+  if (int rc = copy_out(h, nodes4, h->hnodes + env * M * 4, M * 4 * 4)) return rc;
+  if (int rc = copy_out(h, senders, h->hsenders + env * M * 4, M * 4 * 4)) return rc;
+  if (int rc = copy_out(h, discovered, h->discovered + env * M, M)) return rc;
+  CV_HIP(hipStreamSynchronize(h->stream));
+  return check_err(h);
+}
+
 int cov_sync(cov_handle* h) {
   if (!h) return cfail(GF_EINVAL, "null handle");
   if (int rc = use(h)) return rc;
@@ -1538,4 +1681,8 @@ int cov_sync(cov_handle* h) {
 // C-ABI, tests/asan) gets its kernels and launchers here, with this file's flags.
 #ifndef GF_ARL_OWN_TU
 #include "coverage_arl.hip"
+#endif
+// coverage_hidden.hip likewise (GF_HIDDEN_OWN_TU)
+#ifndef GF_HIDDEN_OWN_TU
+#include "coverage_hidden.hip"
 #endif

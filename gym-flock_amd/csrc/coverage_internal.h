@@ -472,10 +472,47 @@ size_t cov_submap_lds_bytes(int P);
 hipError_t launch_cov_pool(const CovPoolArgs& a, hipStream_t s);
 hipError_t launch_cov_submap(const CovSubmapArgs& a, hipStream_t s);
 
+// The radius test `0 < sqrt(dx*dx + dy*dy) <= r` exactly as np.linalg.norm rounds it, from
+// the squared distance s: sqrt is correctly rounded and monotonic, so s at or below r2lo =
+// r*r*(1 - 2^-50) always passes and s above r2hi = r*r*(1 + 2^-50) never does (the margins
+// exceed the roundings of r*r and of the square root by far); only s between them takes
+// the square root. 0 < sqrt(s) iff 0 < s; a NaN s fails both ways.
+__device__ __forceinline__ bool within_radius(double s, double r, double r2lo, double r2hi) {
+  return s > 0.0 && (s <= r2lo || (s <= r2hi && sqrt(s) <= r));
+}
+
+// Hidden-node observation (coverage_hidden.hip; coverage.py:334-346 with hide_nodes=True).
+struct CovHiddenArgs {
+  int B, R, M, Tmax;
+  double radius;             // 4 * DELTA (coverage.py:335)
+  const int32_t* ntg;        // (B)
+  const double* tgt;         // (B,Tmax,2)
+  const double* xr;          // (B,R,2)
+  const uint8_t* visited;    // (B,Tmax)
+  const float* nodes;        // (B,M,3) the ordinary node rows
+  const int32_t* senders;    // (B,4M) the stored senders
+  const int32_t* receivers;  // (B,4M)
+  const int32_t* n_motion;   // (B)
+  uint8_t* discovered;       // (B,M) persistent: 1 robots and discovered targets
+  float* hnodes;             // (B,M,4) out: masked rows + the frontier flag
+  int32_t* hsenders;         // (B,4M) out: senders, -1 where an end is undiscovered (tail kept)
+  uint8_t* gmask;            // (B,Tmax) out: visited | !discovered (the expert's mask)
+  int32_t* ngmask;           // (B) out: masked targets
+  int32_t* nkeep;            // (B) out: slots of hsenders that are not -1
+};
+size_t cov_hidden_lds_bytes(int R, int M);
+hipError_t launch_cov_hidden(const CovHiddenArgs& a, hipStream_t s);
+// discovered := robots only, for the n envs listed (envs == nullptr: envs 0..n-1)
+hipError_t launch_cov_hidden_reset(const CovHiddenArgs& a, const int32_t* envs, int n, hipStream_t s);
+// the unpack_obs tuple's edges of the hidden observation (kept slots compacted at off[b])
+hipError_t launch_cov_hidden_graphs(const CovHiddenArgs& a, const float* edges_in, const int64_t* off, bool mask_all,
+                                    float* edges, int32_t* snd, int32_t* rcv, hipStream_t s);
+
 size_t cov_step_lds_bytes(int R, int M);
-// Observation wire formats: the flat FlattenDictWrapper rows (B, 15M+1) and the
-// batched unpack_obs graph tuple (edges compacted at off[b]).
-hipError_t launch_cov_flat_obs(const CovArgs& a, void* dst, bool f32, hipStream_t s);
+// Observation wire formats: the flat FlattenDictWrapper rows (B, (12 + nf) M + 1), nf
+// features per row of a.nodes, and the batched unpack_obs graph tuple (edges compacted at
+// off[b]).
+hipError_t launch_cov_flat_obs(const CovArgs& a, int nf, void* dst, bool f32, hipStream_t s);
 hipError_t launch_cov_graphs(const CovArgs& a, const int64_t* off, bool mask_all, float* edges, int32_t* snd,
                              int32_t* rcv, hipStream_t s);
 hipError_t launch_cov_graph(const CovArgs& a, const int32_t* envs, int n, hipStream_t s);

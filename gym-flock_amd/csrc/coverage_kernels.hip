@@ -45,14 +45,8 @@ __device__ __forceinline__ double dist2d(double ax, double ay, double bx, double
 // Motion graph of one env (utils.py:8-24 with self_loops=True, coverage.py:572-594):
 // every ordered target pair with 0 < |p_i - p_j| <= radius, in row-major order, which
 // per sender is ascending receiver order (what np.where returns in get_action_edges).
-// The radius test of the motion graph, `0 < sqrt(dx*dx + dy*dy) <= r` exactly as dist2d
-// rounds it, from the squared distance s: sqrt is correctly rounded and monotonic, so s at
-// or below r2lo = r*r*(1 - 2^-50) always passes and s above r2hi = r*r*(1 + 2^-50) never
-// does (the margins exceed the roundings of r*r and of the square root by far); only s
-// between them takes the square root. 0 < sqrt(s) iff 0 < s; a NaN s fails both ways.
-__device__ __forceinline__ bool within_radius(double s, double r, double r2lo, double r2hi) {
-  return s > 0.0 && (s <= r2lo || (s <= r2hi && sqrt(s) <= r));
-}
+// The radius test (within_radius, coverage_internal.h) decides `0 < sqrt(dx*dx + dy*dy) <= r`
+// exactly as dist2d rounds it, from the squared distance.
 
 // Targets staged in LDS with a cell grid (GRID, when Tmax <= kGraphLdsTargets): cells of
 // side h = radius (1 + 2^-20) over the targets' bounding box, so every target within the
@@ -963,26 +957,27 @@ __global__ __launch_bounds__(64) void cov_seed_reset_kernel(CovArgs a, uint32_t 
 // FlattenDictWrapper order (reference test.py:33, keys coverage.py:90): nodes (M,3),
 // edges (4M,1), senders (4M), receivers (4M), step (1,1), concatenated per env. The
 // wrapper's np.concatenate promotes to float64; every value here is exact in float32
-// too (the Box the wrapper declares), so both widths are offered.
+// too (the Box the wrapper declares), so both widths are offered. nf: features per node
+// row of a.nodes (3; 4 with a.nodes / a.senders pointing at the hidden observation).
 template <class V>
-__global__ __launch_bounds__(kCovThreads) void cov_flat_obs_kernel(CovArgs a, V* dst) {
+__global__ __launch_bounds__(kCovThreads) void cov_flat_obs_kernel(CovArgs a, int nf, V* dst) {
   const int b = blockIdx.y;
-  const size_t M = a.M, E = 4 * M, L = 15 * M + 1;
+  const size_t M = a.M, E = 4 * M, N = (size_t)nf * M, L = N + 12 * M + 1;
   V* out = dst + (size_t)b * L;
-  const float* nodes = a.nodes + (size_t)b * 3 * M;
+  const float* nodes = a.nodes + (size_t)b * N;
   const float* edges = a.edges + (size_t)b * E;
   const int32_t* snd = a.senders + (size_t)b * E;
   const int32_t* rcv = a.receivers + (size_t)b * E;
   for (size_t k = (size_t)blockIdx.x * kCovThreads + threadIdx.x; k < L; k += (size_t)gridDim.x * kCovThreads) {
     V v;
-    if (k < 3 * M)
+    if (k < N)
       v = static_cast<V>(nodes[k]);
-    else if (k < 7 * M)
-      v = static_cast<V>(edges[k - 3 * M]);
-    else if (k < 11 * M)
-      v = static_cast<V>(snd[k - 7 * M]);
-    else if (k < 15 * M)
-      v = static_cast<V>(rcv[k - 11 * M]);
+    else if (k < N + 4 * M)
+      v = static_cast<V>(edges[k - N]);
+    else if (k < N + 8 * M)
+      v = static_cast<V>(snd[k - N - 4 * M]);
+    else if (k < N + 12 * M)
+      v = static_cast<V>(rcv[k - N - 8 * M]);
     else
       v = static_cast<V>(a.obs_step[b]);
     out[k] = v;
@@ -1021,13 +1016,13 @@ __global__ __launch_bounds__(kCovThreads) void cov_graphs_kernel(CovArgs a, cons
 
 }  // namespace
 
-hipError_t launch_cov_flat_obs(const CovArgs& a, void* dst, bool f32, hipStream_t s) {
-  const size_t L = 15 * (size_t)a.M + 1;
+hipError_t launch_cov_flat_obs(const CovArgs& a, int nf, void* dst, bool f32, hipStream_t s) {
+  const size_t L = (size_t)(12 + nf) * a.M + 1;
   const dim3 grid((unsigned)((L + 4 * kCovThreads - 1) / (4 * kCovThreads)), a.B);
   if (f32)
-    hipLaunchKernelGGL(cov_flat_obs_kernel<float>, grid, dim3(kCovThreads), 0, s, a, static_cast<float*>(dst));
+    hipLaunchKernelGGL(cov_flat_obs_kernel<float>, grid, dim3(kCovThreads), 0, s, a, nf, static_cast<float*>(dst));
   else
-    hipLaunchKernelGGL(cov_flat_obs_kernel<double>, grid, dim3(kCovThreads), 0, s, a, static_cast<double*>(dst));
+    hipLaunchKernelGGL(cov_flat_obs_kernel<double>, grid, dim3(kCovThreads), 0, s, a, nf, static_cast<double*>(dst));
   return hipGetLastError();
 }
 

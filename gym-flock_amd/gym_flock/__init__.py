@@ -21,6 +21,8 @@ ENV_IDS = {
     "CoverageFull-v0": ("gym_flock.envs.spatial:CoverageFullEnv", 100000),          # :21-25
     "CoverageARL-v1": ("gym_flock.envs.spatial:CoverageARLEnv", 100000),            # :27-31
     "CoverageARL-v0": ("gym_flock.envs.spatial:CoverageARLEnv", 100000),            # :34-38
+    "ExploreEnv-v0": ("gym_flock.envs.spatial:ExploreEnv", 100000),                 # :3-7
+    "ExploreEnv-v1": ("gym_flock.envs.spatial:ExploreEnv", 100000),                 # :15-19
 }
 
 if HAVE_GYM:  # pragma: no cover - gym is not installed in the build image

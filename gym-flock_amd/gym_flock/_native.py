@@ -216,6 +216,8 @@ SIGNATURES = {
     "cov_get_flat_obs": [_P, _P, _I],
     "cov_graphs_tuple_sizes": [_P, _P, _P, _I],
     "cov_get_graphs_tuple": [_P, _P, _P, _P, _P, _P, _P, _P, _I],
+    "cov_set_hidden": [_P, _I],
+    "cov_get_hidden_obs": [_P, _I, _P, _P, _P],
     "gu_create": [_I, ctypes.POINTER(_P)],
     "gu_destroy": [_P],
     "gu_radius_edges": [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_double, _I,
@@ -771,6 +773,7 @@ class CoverageHandle:
                              float(res), float(motion_radius), int(device), int(horizon))
         self.n_robots, self.n_envs, self.max_nodes = int(n_robots), int(n_envs), int(max_nodes)
         self.t_max = self.max_nodes - self.n_robots
+        self.n_node_feat = 3  # 4 once set_hidden(True)
         h = ctypes.c_void_p()
         check(self.lib.cov_create(ctypes.byref(self.cfg), ctypes.byref(h)))
         self.h = h
@@ -986,6 +989,33 @@ class CoverageHandle:
         check(self.lib.cov_get_obs(self.h, int(env), ptr(nodes), ptr(edges), ptr(snd), ptr(rcv), ptr(step)))
         return {"nodes": nodes, "edges": edges, "senders": snd, "receivers": rcv, "step": step}
 
+    def set_hidden(self, enable=True):
+        """Hidden nodes (cov_set_hidden; ExploreEnv): every observation is followed by the
+        device pass that grows the discovered set and writes the masked 4-feature node rows,
+        the frontier flag and the hidden senders."""
+        check(self.lib.cov_set_hidden(self.h, 1 if enable else 0))
+        self.n_node_feat = 4 if enable else 3
+
+    def hidden_obs(self, env=0):
+        """The hidden observation of one env as the reference returns it: float64 (M,4)
+        nodes (coverage.py:337 rebinds them to the product with the float64 discovered
+        column), the hidden senders; edges, receivers and step as in obs()."""
+        m = self.max_nodes
+        nodes = np.empty((m, 4), np.float32)
+        snd = np.empty(4 * m, np.int32)
+        edges = np.empty((4 * m, 1), np.float32)
+        rcv = np.empty(4 * m, np.int32)
+        step = np.empty((1, 1), np.int64)
+        check(self.lib.cov_get_hidden_obs(self.h, int(env), ptr(nodes), ptr(snd), None))
+        check(self.lib.cov_get_obs(self.h, int(env), None, ptr(edges), None, ptr(rcv), ptr(step)))
+        return {"nodes": nodes.astype(np.float64), "edges": edges, "senders": snd, "receivers": rcv, "step": step}
+
+    def discovered(self, env=0):
+        """(max_nodes) uint8: 1 for the robots and every target discovered so far."""
+        d = np.empty(self.max_nodes, np.uint8)
+        check(self.lib.cov_get_hidden_obs(self.h, int(env), None, None, ptr(d)))
+        return d
+
     def motion_edges(self, env=0, n=None):
         """The first n (default: the env's motion-edge count) senders and receivers of env's
         observation, i.e. its motion graph (global node indices), without the rest."""
@@ -1041,14 +1071,15 @@ class CoverageHandle:
         return a, rnd.astype(bool)
 
     def flat_obs(self, f32=False, device_ptr=None):
-        """(B, 15*max_nodes + 1) rows in FlattenDictWrapper order (float64 like its
-        np.concatenate, or float32). device_ptr: write into that device buffer instead
+        """(B, (12 + n_node_feat) * max_nodes + 1) rows in FlattenDictWrapper order (float64
+        like its np.concatenate, or float32); the hidden observation on a handle with
+        set_hidden. device_ptr: write into that device buffer instead
         (asynchronous on the handle's stream; returns None)."""
         flags = COV_FLAT_F32 if f32 else 0
         if device_ptr is not None:
             check(self.lib.cov_get_flat_obs(self.h, ctypes.c_void_p(int(device_ptr)), flags | COV_OUT_DEVICE))
             return None
-        out = np.empty((self.n_envs, 15 * self.max_nodes + 1), np.float32 if f32 else np.float64)
+        out = np.empty((self.n_envs, (12 + self.n_node_feat) * self.max_nodes + 1), np.float32 if f32 else np.float64)
         check(self.lib.cov_get_flat_obs(self.h, ptr(out), flags))
         return out
 
@@ -1060,7 +1091,7 @@ class CoverageHandle:
         tot = ctypes.c_int64()
         check(self.lib.cov_graphs_tuple_sizes(self.h, ptr(ne), ctypes.byref(tot), flags))
         T = int(tot.value)
-        o = dict(n_node=np.empty(self.n_envs, np.int32), nodes=np.empty((self.n_envs * self.max_nodes, 3), np.float32),
+        o = dict(n_node=np.empty(self.n_envs, np.int32), nodes=np.empty((self.n_envs * self.max_nodes, self.n_node_feat), np.float32),
                  n_edge=np.empty(self.n_envs, np.int32), edges=np.empty((T, 1), np.float32),
                  senders=np.empty(T, np.int32), receivers=np.empty(T, np.int32),
                  globs=np.empty((self.n_envs, 1), np.float32))

@@ -11,8 +11,9 @@ the target map (global np.random, maps.generate_targets) and reset()'s start and
 unvisited draws (self.np_random), in the reference's call order.
 
 Supported configuration: the module constants the reference ships with (PAD_ACTIONS,
-COLLISION_CHECKS, PAD_NODES, distance edge features, HIDE_NODES False; pad_nodes=False only
-for an env whose maps all have the same node count, CoverageFull-v0). Like the
+COLLISION_CHECKS, PAD_NODES, distance edge features; hide_nodes only with n_node_feat=4, the
+frontier flag, as ExploreEnv sets them; pad_nodes=False only for an env whose maps all have
+the same node count, CoverageFull-v0). Like the
 reference, observations alias buffers that the next step overwrites only in the sense
 that each call returns fresh host copies of the device arrays.
 """
@@ -51,9 +52,9 @@ class CoverageEnv(Env):
                  nearby_starts=NEARBY_STARTS, horizon=HORIZON, hide_nodes=False,
                  n_node_feat=N_NODE_FEAT, device=0):
         super(CoverageEnv, self).__init__()
-        if hide_nodes or n_node_feat != N_NODE_FEAT:
-            raise NotImplementedError("only the reference's shipped configuration (no hidden nodes, "
-                                      "3 node features) is implemented")
+        if bool(hide_nodes) != (n_node_feat == N_NODE_FEAT + 1) or n_node_feat not in (N_NODE_FEAT, N_NODE_FEAT + 1):
+            raise NotImplementedError("only the reference's shipped configurations are implemented: no hidden "
+                                      "nodes with 3 node features, or hide_nodes=True with n_node_feat=4 (ExploreEnv)")
         if not pad_nodes and not self._fixed_node_count():
             # max_nodes = n_agents (coverage.py:540-541) sizes the device arrays: the node count
             # has to be known before the handle is made, and must not change with the map
@@ -123,6 +124,8 @@ class CoverageEnv(Env):
             self._h.close()
         self._h = nat.CoverageHandle(self.n_robots, 1, self.max_nodes, self.episode_length, self.res,
                                      self.motion_radius, self.device, horizon=self.horizon)
+        if self.hide_nodes:
+            self._h.set_hidden(True)
 
     # --------------------------------------------------------------- graph setup
     def _generate_targets(self):
@@ -219,7 +222,7 @@ class CoverageEnv(Env):
         self.step_counter = 1
         self._closest = starts.astype(np.int64) + self.n_robots  # robots sit on their start targets
         self._greedy_cache = None
-        return self._h.obs(0)
+        return self._obs()
 
     def step(self, action):
         """coverage.py:174-204 (with _get_obs_reward :234-364). In the default fetch mode
@@ -235,7 +238,9 @@ class CoverageEnv(Env):
         if a.shape[0] != self.n_robots or np.any((a < 0) | (a >= self.n_actions)):
             raise IndexError("each robot's action must be in [0, %d)" % self.n_actions)
         self.last_loc = self._closest if self._closest is not None else self.closest_targets
-        if self.fetch_mode != "direct":
+        if self.fetch_mode != "direct" or self.hide_nodes:
+            # hidden nodes: the observation is the device's hidden pass after the step (the
+            # one-call step writes the unhidden one)
             self._h.step(a[None])
             self._closest = self._greedy_cache = None
             return self._obs_reward()
@@ -277,8 +282,19 @@ class CoverageEnv(Env):
         self.episode_reward += reward
         return {"nodes": nodes, "edges": edges, "senders": snd, "receivers": rcv, "step": stp}, reward, done, {}
 
+    def _obs(self):
+        return self._h.hidden_obs(0) if self.hide_nodes else self._h.obs(0)
+
+    @property
+    def discovered_nodes(self):
+        """(max_nodes, 1) float: 1 for the robots and every target discovered so far
+        (coverage.py:419-421, :336); hide_nodes only."""
+        if not self.hide_nodes:
+            raise AttributeError("discovered_nodes exists with hide_nodes=True only")
+        return self._h.discovered(0).astype(np.float64).reshape(-1, 1)
+
     def _obs_reward(self):
-        obs = self._h.obs(0)
+        obs = self._obs()
         r, d = self._h.rewards()
         reward, done = float(r[0]), bool(d[0])
         self.step_counter += 1
@@ -323,8 +339,10 @@ class CoverageEnv(Env):
             return self.np_random.choice(self.n_actions, size=(self.n_robots, 1))
         if not greedy:
             raise AssertionError("Vehicle routing controller is not available if OR-Tools is not imported.")
-        self._want_greedy = True
-        if self._greedy_cache is not None:  # computed by the step that made this state
+        # hidden nodes: undiscovered targets are masked like visited ones (:819-820), by
+        # cov_controller_greedy alone
+        self._want_greedy = not self.hide_nodes
+        if self._greedy_cache is not None and not self.hide_nodes:  # computed by the step that made this state
             a, rnd = self._greedy_cache
             a = a.copy()
         else:

@@ -144,14 +144,21 @@ class VecCoverage:
     then load_occupancy(grid); reset(new_maps=True) then samples every env's map from the
     pool (generate_submaps). The batched reset keeps uniform starts (cov_reset_seeded):
     the reference's nearby_starts region is drawn by the drop-in CoverageARLEnv only.
+
+    ExploreEnv batches: the same with hide_nodes=True (and horizon=19). obs(), flat_obs()
+    and graphs_tuple() then give the hidden observation (4 node features, hidden senders),
+    step(greedy=True) masks undiscovered targets, and expert_steps() is refused.
     """
 
     def __init__(self, n_envs, n_robots, max_nodes=1000, episode_length=75, res=5.5,
-                 frac_active_targets=0.5, device=0, env_offset=0):
+                 frac_active_targets=0.5, device=0, env_offset=0, hide_nodes=False, horizon=10):
         self.n_envs, self.n_robots = int(n_envs), int(n_robots)
         self.frac = frac_active_targets
         self.env_offset = int(env_offset)
-        self.h = nat.CoverageHandle(n_robots, n_envs, max_nodes, episode_length, res, None, device)
+        self.hide_nodes = bool(hide_nodes)
+        self.h = nat.CoverageHandle(n_robots, n_envs, max_nodes, episode_length, res, None, device, horizon=horizon)
+        if self.hide_nodes:
+            self.h.set_hidden(True)
         self.n_targets = np.zeros(self.n_envs, np.int64)
         self._rngs = None          # host-held np_random streams (else on the device)
         self._dev_streams = False  # the device holds every env's np_random stream
@@ -251,8 +258,8 @@ class VecCoverage:
         """Whether the fused greedy step can draw the fallback robots' np_random.choice(4)
         on the device (COV_GREEDY_RNG): the streams live there, n_robots <= 624 (one key
         regeneration per step) and the per-node greedy lists exist (max_nodes - n_robots
-        <= 1024)."""
-        return self._dev_streams and self._rngs is None and self.n_robots <= 624 and self.h.t_max <= 1024
+        <= 1024). Never with hidden nodes: the fused step does not know the discovered set."""
+        return not self.hide_nodes and self._dev_streams and self._rngs is None and self.n_robots <= 624 and self.h.t_max <= 1024
 
     def _host_rngs(self):
         """The envs' np_random streams as host RandomStates (read back from the device the
@@ -297,6 +304,9 @@ class VecCoverage:
                         a[b, k] = rngs[b].choice(4, size=len(k))
                     self.h.set_actions(a)
                 rc = self.h._step_resident()
+            elif greedy and self.hide_nodes:  # fallback="zero": the masked expert, then a resident step
+                self.h.controller_greedy(fetch=False)
+                rc = self.h._step_resident()
             elif greedy:
                 rc = self.h._step_greedy_rng() if fallback == "draw" else self.h._step_greedy()
             else:
@@ -314,6 +324,8 @@ class VecCoverage:
         draws="device", or R <= 624 with host draws) and the greedy lists
         (max_nodes - n_robots <= 1024). Returns (rewards (n_steps,B), done (n_steps,B)) or
         None with fetch=False."""
+        if self.hide_nodes:
+            return self.h.step_expert(n_steps, fetch=fetch)  # the library refuses it (GF_EINVAL)
         if not self._device_draws():
             raise RuntimeError("expert_steps needs the envs' np_random streams on the device, n_robots <= 624 "
                                "and max_nodes - n_robots <= 1024")
@@ -326,10 +338,11 @@ class VecCoverage:
         return self.h.rewards()
 
     def obs(self, env=0):
-        return self.h.obs(env)
+        return self.h.hidden_obs(env) if self.hide_nodes else self.h.obs(env)
 
     def flat_obs(self, f32=False, device_ptr=None):
-        """Every env's observation as one FlattenDictWrapper row (B, 15*max_nodes + 1)."""
+        """Every env's observation as one FlattenDictWrapper row (B, 15*max_nodes + 1), or
+        (B, 16*max_nodes + 1) with hidden nodes."""
         return self.h.flat_obs(f32, device_ptr)
 
     def graphs_tuple(self, mask_all=False):

@@ -515,6 +515,38 @@ int cov_graphs_tuple_sizes(cov_handle* h, int32_t* n_edge, int64_t* total_edges,
 int cov_get_graphs_tuple(cov_handle* h, int32_t* n_node, float* nodes, int32_t* n_edge, float* edges,
                          int32_t* senders, int32_t* receivers, float* globs, int flags);
 
+/* Hidden nodes (ExploreEnv-v0 / -v1: hide_nodes=True, n_node_feat=4; coverage.py:334-346).
+ * enable = 1 allocates the hidden observation and sets every env's discovered set to the
+ * robots only; from then on every call that makes an observation (cov_reset,
+ * cov_reset_seeded, cov_step with host, device or resident actions) is followed on the
+ * handle's stream by a pass that
+ *   - adds to the env's discovered set every target within 0 < r <= 4 * 5.5 of a robot (the
+ *     reference's module constant DELTA, whatever the env's res; a robot does not see the
+ *     node it stands on, r = 0),
+ *   - writes the node rows (max_nodes, 4): the three features times the discovered flag,
+ *     then the frontier flag (1 on a discovered receiver of an edge slot whose sender is
+ *     undiscovered, over all 4 * max_nodes slots),
+ *   - writes the senders with -1 in every slot that has an undiscovered end, the last
+ *     8 * n_robots action-edge slots excepted.
+ * cov_reset / cov_reset_seeded set discovered back to the robots only before their
+ * observation, and so do cov_set_targets, cov_generate_maps and cov_generate_submaps for
+ * the envs they touch; cov_set_robot_positions leaves it alone. On such a handle
+ *   - cov_get_obs keeps returning the unhidden 3-feature observation,
+ *   - cov_controller_greedy masks visited OR undiscovered targets (controller :817-821,
+ *     with its np.where quirk: target 0 is masked too once any target is masked),
+ *   - cov_get_flat_obs rows are 16 * max_nodes + 1 wide (nodes (max_nodes, 4), edges, the
+ *     hidden senders, receivers, step), and the graph tuple has (B * max_nodes, 4) nodes
+ *     and drops the slots whose hidden sender is -1 (graph 0 only, or all: COV_MASK_ALL),
+ *   - the fused expert forms (COV_ACTIONS_GREEDY, COV_NEXT_GREEDY, cov_step_expert,
+ *     cov_step_host) return GF_EINVAL: they read the visited flags inside the step.
+ * enable = 0 turns the pass off again. A handle that never enables it launches and
+ * allocates nothing for it. */
+int cov_set_hidden(cov_handle* h, int enable);
+/* The hidden observation of one env: nodes4 (max_nodes, 4) f32, senders (4 * max_nodes)
+ * i32, discovered (max_nodes) u8. Any pointer may be NULL. Edges, receivers and step are
+ * cov_get_obs'. GF_ESTATE when the handle does not hide nodes. */
+int cov_get_hidden_obs(cov_handle* h, int env, float* nodes4, int32_t* senders, uint8_t* discovered);
+
 /* Graph helpers of gym_flock/envs/spatial/utils.py ------
  * A context owns device scratch and the last edge list. Positions are host float64
  * (n, 2) arrays; pos2 == NULL means pos2 = pos1 (the reference's pos2=None), with the
@@ -562,7 +594,8 @@ int fe_set_streams(fe_handle* h, int n);
 /* Order the handle's stream after all of its outstanding work (enqueue only, no host
  * wait): for zero-copy consumers that enqueue on fe_buffers.stream after fe_step. */
 int fe_join(fe_handle* h);
-/* The same for cov_step_kernel on a Coverage handle. */
+/* The same for cov_step_kernel on a Coverage handle (on a handle that hides nodes, the
+ * step kernel and the hidden pass behind it). */
 int cov_kernel_timing(cov_handle* h, int enable, double* avg_ms, int64_t* launches);
 /* Diagnostics for roofline work: what = 0/1 times `reps` launches of a float4
  * plain/non-temporal fill of the network buffer (the write-bandwidth ceiling).
