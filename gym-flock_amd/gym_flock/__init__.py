@@ -23,6 +23,7 @@ ENV_IDS = {
     "CoverageARL-v0": ("gym_flock.envs.spatial:CoverageARLEnv", 100000),            # :34-38
     "ExploreEnv-v0": ("gym_flock.envs.spatial:ExploreEnv", 100000),                 # :3-7
     "ExploreEnv-v1": ("gym_flock.envs.spatial:ExploreEnv", 100000),                 # :15-19
+    "Shepherding-v0": ("gym_flock.envs.shepherding:ShepherdingEnv", 1000),         # :47-51
 }
 
 if HAVE_GYM:  # pragma: no cover - gym is not installed in the build image

@@ -124,6 +124,21 @@ COV_NEXT_GREEDY = 0x40
 COV_GREEDY_RNG = 0x80
 
 
+class ShepConfig(ctypes.Structure):
+    _fields_ = [("n_shepherds", ctypes.c_int32), ("n_sheep", ctypes.c_int32), ("n_envs", ctypes.c_int32),
+                ("dt", ctypes.c_double), ("comm_radius", ctypes.c_double), ("action_scalar", ctypes.c_double),
+                ("force_weight_shepherd", ctypes.c_double), ("force_weight_sheep", ctypes.c_double),
+                ("goal_region_radius", ctypes.c_double), ("device", ctypes.c_int32)]
+
+
+SHEP_U_DEVICE = 0x02
+SHEP_U_F64 = 0x04
+SHEP_U_EXPERT = 0x08
+SHEP_U_RESIDENT = 0x80
+SHEP_OUT_DEVICE = 0x4
+SHEP_OUT_F32 = 0x8
+
+
 class GymFlockError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libgymflock error %d: %s" % (code, msg))
@@ -226,6 +241,20 @@ SIGNATURES = {
                    ctypes.POINTER(ctypes.c_int64)],
     "gu_get_edges": [_P, _P, _P, _P, _P],
     "gu_nodes_within_radius": [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_double, _P],
+    "shep_create": [ctypes.POINTER(ShepConfig), ctypes.POINTER(_P)],
+    "shep_destroy": [_P],
+    "shep_set_state": [_P, _P],
+    "shep_get_state": [_P, _P],
+    "shep_observe": [_P],
+    "shep_step": [_P, _P, _I],
+    "shep_controller": [_P, _P],
+    "shep_step_expert": [_P, _I, _P],
+    "shep_get_obs": [_P, _P, _I],
+    "shep_get_adj": [_P, _P, _I],
+    "shep_get_rewards": [_P, _P, _I],
+    "shep_get_outputs": [_P, _P],
+    "shep_get_controls": [_P, _P],
+    "shep_sync": [_P],
     "fe_last_error": [],
     "fe_abi_version": [],
     "fe_diag": [_P, _I, _I, ctypes.POINTER(ctypes.c_double)],
@@ -1105,6 +1134,118 @@ class CoverageHandle:
         p = np.empty((n_targets, n_targets), np.int32)
         check(self.lib.cov_get_time_matrix(self.h, int(env), ptr(c), ptr(p)))
         return c, p
+
+
+class ShepherdHandle:
+    """Owns one shep_handle: B Shepherding-v0 envs of n_shepherds + n_sheep agents."""
+
+    def __init__(self, n_shepherds=10, n_sheep=20, n_envs=1, dt=0.01, comm_radius=2.0, action_scalar=5.0,
+                 force_weights=None, goal_region_radius=None, device=0):
+        self.lib = load()
+        n = int(n_shepherds) + int(n_sheep)
+        # the reference's host arithmetic (shepherding.py:50 and :39, :43), in float64
+        fw = (0.15 * 3.0, 0.15 * 0.5) if force_weights is None else force_weights
+        if goal_region_radius is None:
+            goal_region_radius = 0.5 * (1.0 * np.sqrt(n)) if n > 0 else 0.0
+        self.cfg = ShepConfig(int(n_shepherds), int(n_sheep), int(n_envs), float(dt), float(comm_radius),
+                              float(action_scalar), float(fw[0]), float(fw[1]), float(goal_region_radius),
+                              int(device))
+        self.n_shepherds, self.n_sheep, self.n_agents, self.n_envs = int(n_shepherds), int(n_sheep), n, int(n_envs)
+        h = ctypes.c_void_p()
+        check(self.lib.shep_create(ctypes.byref(self.cfg), ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h:
+            self.lib.shep_destroy(h)
+            h.value = None
+            self.h = None
+
+    __del__ = close
+
+    def set_state(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.shape == (self.n_envs, self.n_agents, 3), x.shape
+        check(self.lib.shep_set_state(self.h, ptr(x)))
+
+    def get_state(self):
+        x = np.empty((self.n_envs, self.n_agents, 3))
+        check(self.lib.shep_get_state(self.h, ptr(x)))
+        return x
+
+    def observe(self):
+        check(self.lib.shep_observe(self.h))
+
+    def step(self, u=None, flags=0):
+        """u: host ndarray (B,n_shepherds,2) (float32 arithmetic for float32 / float16
+        actions, else float64, as NumPy promotes u * 5.0), or a device pointer (int) with
+        SHEP_U_DEVICE (float32 unless SHEP_U_F64), or None with SHEP_U_EXPERT /
+        SHEP_U_RESIDENT."""
+        if flags & (SHEP_U_EXPERT | SHEP_U_RESIDENT):
+            check(self.lib.shep_step(self.h, None, int(flags)))
+        elif flags & SHEP_U_DEVICE:
+            check(self.lib.shep_step(self.h, ctypes.c_void_p(int(u)), int(flags)))
+        else:
+            u = np.asarray(u)
+            if u_is_f64(u):
+                flags |= SHEP_U_F64
+                u = u.astype(np.float64, copy=False)
+            else:
+                u = u.astype(np.float32, copy=False)
+                flags &= ~SHEP_U_F64
+            u = np.ascontiguousarray(u)
+            assert u.shape == (self.n_envs, self.n_shepherds, 2), u.shape
+            check(self.lib.shep_step(self.h, ptr(u), int(flags)))
+
+    def controller(self, fetch=True):
+        """controller() of every env (B,n_shepherds,2) float64; it also becomes the resident
+        action buffer. fetch=False leaves it there (no synchronisation)."""
+        out = np.empty((self.n_envs, self.n_shepherds, 2)) if fetch else None
+        check(self.lib.shep_controller(self.h, ptr(out)))
+        return out
+
+    def step_expert(self, n_steps, fetch=True):
+        """n_steps closed-loop steps in one launch; every step's rewards (n_steps,B), or
+        None with fetch=False (asynchronous)."""
+        r = np.empty((int(n_steps), self.n_envs)) if fetch else None
+        check(self.lib.shep_step_expert(self.h, int(n_steps), ptr(r)))
+        return r
+
+    def _out(self, fn, shape, f32, device_ptr):
+        flags = SHEP_OUT_F32 if f32 else 0
+        if device_ptr is not None:
+            check(fn(self.h, ctypes.c_void_p(int(device_ptr)), flags | SHEP_OUT_DEVICE))
+            return None
+        out = np.empty(shape, np.float32 if f32 else np.float64)
+        check(fn(self.h, ptr(out), flags))
+        return out
+
+    def obs(self, f32=False, device_ptr=None):
+        return self._out(self.lib.shep_get_obs, (self.n_envs, self.n_agents, 4), f32, device_ptr)
+
+    def adj(self, f32=False, device_ptr=None):
+        return self._out(self.lib.shep_get_adj, (self.n_envs, self.n_agents, self.n_agents), f32, device_ptr)
+
+    def rewards(self, f32=False, device_ptr=None):
+        return self._out(self.lib.shep_get_rewards, (self.n_envs,), f32, device_ptr)
+
+    def outputs(self):
+        """(obs (B,N,4), adj (B,N,N), rewards (B)) in one copy and one wait
+        (shep_get_outputs); the three are views of one array."""
+        b, n = self.n_envs, self.n_agents
+        buf = np.empty(b * n * (4 + n) + b)
+        check(self.lib.shep_get_outputs(self.h, ptr(buf)))
+        return (buf[:b * n * 4].reshape(b, n, 4), buf[b * n * 4:b * n * (4 + n)].reshape(b, n, n),
+                buf[b * n * (4 + n):])
+
+    def controls(self):
+        out = np.empty((self.n_envs, self.n_agents, 2))
+        check(self.lib.shep_get_controls(self.h, ptr(out)))
+        return out
+
+    def sync(self):
+        check(self.lib.shep_sync(self.h))
 
 
 class GraphUtils:

@@ -42,3 +42,16 @@ def synthetic_batch(n_envs, n_agents, seed0=0, v_max=5.0):
     for b in range(n_envs):
         out[b] = synthetic_state(n_agents, seed0 + b, v_max)
     return out
+
+
+def draw_shepherding(n_agents, r_max, goal_offset, rs):
+    """Shepherding's reset() draw (shepherding.py:193-200) from RandomState `rs`: lengths
+    first, then angles, on a disk of radius sqrt(r_max) moved by goal_offset; (N,2) x, y."""
+    length = np.sqrt(rs.uniform(0, r_max, size=(n_agents,)))
+    angle = np.pi * rs.uniform(0, 2, size=(n_agents,))
+    xy = np.empty((n_agents, 2))
+    xy[:, 0] = length * np.cos(angle)
+    xy[:, 1] = length * np.sin(angle)
+    xy[:, 0] += goal_offset[0]
+    xy[:, 1] += goal_offset[1]
+    return xy

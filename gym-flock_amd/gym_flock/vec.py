@@ -9,7 +9,7 @@ transfer.
 import numpy as np
 
 from . import _native as nat
-from .init_states import synthetic_batch
+from .init_states import draw_shepherding, synthetic_batch
 
 
 # fe_variant presets of the registered flocking variants (include/gymflock.h)
@@ -348,6 +348,98 @@ class VecCoverage:
     def graphs_tuple(self, mask_all=False):
         """The batch as unpack_obs's graph tuple (coverage.py:689-741)."""
         return self.h.graphs_tuple(mask_all)
+
+    def sync(self):
+        self.h.sync()
+
+    def close(self):
+        self.h.close()
+
+
+class VecShepherding:
+    """B Shepherding-v0 envs (reference gym_flock/envs/shepherding/shepherding.py) of
+    n_shepherds + n_sheep unicycle agents on one GPU, one launch per step for the whole
+    batch; expert_steps(n) runs n closed-loop steps of the heuristic shepherd controller in
+    one launch, the states never leaving the chip.
+
+    The adjacency, the reward and the sheep's controls are the reference's bit for bit for
+    a given state; the integrated state matches it to rounding (the device's cos / sin are
+    not NumPy's to the last bit)."""
+
+    def __init__(self, n_envs, n_shepherds=10, n_sheep=20, dt=0.01, comm_radius=2.0, action_scalar=5.0,
+                 r_max_init=1.0, device=0):
+        self.n_envs, self.n_shepherds, self.n_sheep = int(n_envs), int(n_shepherds), int(n_sheep)
+        self.n_agents = self.n_shepherds + self.n_sheep
+        self.r_max = r_max_init * np.sqrt(self.n_agents)           # :39
+        self.goal_offset = np.array([-self.r_max * 3, 0])          # :42
+        self.goal_region_radius = 0.5 * self.r_max                 # :43
+        self.h = nat.ShepherdHandle(n_shepherds, n_sheep, n_envs, dt, comm_radius, action_scalar,
+                                    goal_region_radius=self.goal_region_radius, device=device)
+
+    # ------------------------------------------------------------------- state
+    def reset(self, seed=0):
+        """Env b draws from RandomState(seed + b) as the reference's reset() does after
+        seed(seed + b) (host draws: the state is the reference's bit for bit; headings start
+        at 0). Returns the (B,N,3) state; obs() / adj() hold its observation."""
+        x = np.zeros((self.n_envs, self.n_agents, 3))
+        for b in range(self.n_envs):
+            rs = np.random.RandomState(seed + b)
+            x[b, :, :2] = draw_shepherding(self.n_agents, self.r_max, self.goal_offset, rs)
+        self.set_state(x)
+        return x
+
+    def set_state(self, x):
+        """A (B,N,3) state and its observation, adjacency and reward."""
+        self.h.set_state(x)
+        self.h.observe()
+
+    def get_state(self):
+        return self.h.get_state()
+
+    # ---------------------------------------------------------------- hot path
+    def step(self, u=None, resident=False, device_ptr=None, expert=False, f64=False):
+        """Advance every env one step. u: (B,n_shepherds,2) host actions (float32 or
+        float64 arithmetic like the reference's u * 5.0); or resident=True to reuse the
+        action buffer (the last host actions or controller() output); or device_ptr=<int>
+        for a device buffer of float32 (f64=True: float64) actions, read on the handle's
+        stream; or expert=True: controller() of the current state computed in the step's
+        launch. Asynchronous."""
+        if expert:
+            self.h.step(None, nat.SHEP_U_EXPERT)
+        elif resident:
+            self.h.step(None, nat.SHEP_U_RESIDENT)
+        elif device_ptr is not None:
+            self.h.step(device_ptr, nat.SHEP_U_DEVICE | (nat.SHEP_U_F64 if f64 else 0))
+        else:
+            self.h.step(u)
+
+    def controller(self, fetch=True):
+        """The heuristic shepherd controller (:204-273) of every env, (B,n_shepherds,2)."""
+        return self.h.controller(fetch)
+
+    def expert_steps(self, n_steps, fetch=True):
+        """n_steps of u = controller(); step(u) in one launch; rewards (n_steps,B)."""
+        return self.h.step_expert(n_steps, fetch)
+
+    # ----------------------------------------------------------------- outputs
+    def obs(self, f32=False, device_ptr=None):
+        """(B,N,4) [x, y, theta, identity]; device_ptr: written there instead (stream-ordered)."""
+        return self.h.obs(f32, device_ptr)
+
+    def adj(self, f32=False, device_ptr=None):
+        """(B,N,N) 1/r within comm_radius, else 0."""
+        return self.h.adj(f32, device_ptr)
+
+    def rewards(self, f32=False, device_ptr=None):
+        return self.h.rewards(f32, device_ptr)
+
+    def outputs(self):
+        """(obs, adj, rewards) as host float64 in one copy and one wait."""
+        return self.h.outputs()
+
+    def controls(self):
+        """(B,N,2) control of the last step: u * action_scalar, then the sheep's repulsion."""
+        return self.h.controls()
 
     def sync(self):
         self.h.sync()

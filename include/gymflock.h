@@ -574,6 +574,74 @@ int gu_get_edges(gu_graph* g, int32_t* senders, int32_t* receivers, double* r, d
 int gu_nodes_within_radius(gu_graph* g, const double* pos1, int32_t n1, const double* pos2, int32_t n2, double rad,
                            uint8_t* valid);
 
+/* Shepherding-v0 (gym_flock/envs/shepherding/shepherding.py) ----------------------
+ * B envs of N = n_shepherds + n_sheep unicycle agents, state (B,N,3) float64 =
+ * [x, y, theta], shepherds first. One launch per call: the step (:80-117) with the sheep's
+ * repulsion controller (:164-178, summed over j in order like np.sum), then the new
+ * state's observation (B,N,4) = [x, y, theta, identity] (:127), adjacency (B,N,N) =
+ * 1/r within comm_radius, 0 on the diagonal and beyond (:139-162), and reward (B) = the
+ * fraction of sheep with |(x, y)| < goal_region_radius (:180-185), all float64. The
+ * adjacency, the reward and the sheep's controls are bit-exact for a given state; cos, sin
+ * and atan2 are the device library's, so the integrated state and the shepherd controller
+ * match NumPy to rounding. One stream per handle; every call is ordered on it. */
+typedef struct shep_config {
+  int32_t n_shepherds;          /* 10 (:28)                                          */
+  int32_t n_sheep;              /* 20 (:27); n_shepherds + n_sheep <= 1024           */
+  int32_t n_envs;               /* B                                                 */
+  double dt;                    /* 0.01 (:33)                                        */
+  double comm_radius;           /* 2.0 (:46)                                         */
+  double action_scalar;         /* 5.0 (:35)                                         */
+  double force_weight_shepherd; /* 0.15 * 3.0 (:50), as the host computed it         */
+  double force_weight_sheep;    /* 0.15 * 0.5 (:50)                                  */
+  double goal_region_radius;    /* 0.5 * (1.0 * sqrt(N)) (:39, :43)                  */
+  int32_t device;               /* HIP device ordinal                                */
+} shep_config;
+typedef struct shep_handle shep_handle;
+
+#define SHEP_U_DEVICE   0x02 /* u is a device pointer (else host)                          */
+#define SHEP_U_F64      0x04 /* u is float64 (else float32): u * action_scalar (:89) is
+                                computed in u's precision, as NumPy does                   */
+#define SHEP_U_EXPERT   0x08 /* u := controller() of the current state, in the same launch */
+#define SHEP_U_RESIDENT 0x80 /* u := the handle's action buffer: the last host actions or
+                                the last shep_controller output                            */
+#define SHEP_OUT_DEVICE 0x4  /* dst is device memory (else host); stream-ordered, shep_sync */
+#define SHEP_OUT_F32    0x8  /* dst is float32 (else float64)                               */
+
+/* GF_EINVAL before any device work for a null pointer, n_shepherds < 1, n_sheep < 1,
+ * N > 1024, n_envs < 1 and a non-positive dt, comm_radius or goal_region_radius. */
+int shep_create(const shep_config* cfg, shep_handle** out);
+int shep_destroy(shep_handle* h);
+int shep_set_state(shep_handle* h, const double* x);   /* (B,N,3) host */
+int shep_get_state(shep_handle* h, double* x);
+/* Observation, adjacency and reward of the state just set (reset() :187-202). */
+int shep_observe(shep_handle* h);
+/* One step. u: (B,n_shepherds,2) shepherd actions in host memory (copied to the handle's
+ * action buffer), or device memory (SHEP_U_DEVICE, read in place on the handle's stream),
+ * or NULL with SHEP_U_RESIDENT / SHEP_U_EXPERT. GF_ESTATE before a state is set. */
+int shep_step(shep_handle* h, const void* u, int flags);
+/* controller() :204-273 of the current state into the handle's action buffer (float64);
+ * out (B,n_shepherds,2) host or NULL (then no synchronisation). The quirk of :253 is kept:
+ * a shepherd is tested for line of sight only when exactly one of the two states has a
+ * component that is exactly zero. */
+int shep_controller(shep_handle* h, double* out);
+/* n_steps of u = controller(); step(u) in one launch, the state held in LDS throughout;
+ * every step's reward to rewards (n_steps,B) host or NULL (then no synchronisation); the
+ * observation and adjacency are the last step's. */
+int shep_step_expert(shep_handle* h, int n_steps, double* rewards);
+/* The last observation (B,N,4), adjacency (B,N,N) and rewards (B) to host memory, or with
+ * SHEP_OUT_DEVICE to caller-owned device memory (e.g. a torch tensor's data_ptr()), as
+ * float64 or with SHEP_OUT_F32 float32. */
+int shep_get_obs(shep_handle* h, void* dst, int flags);
+int shep_get_adj(shep_handle* h, void* dst, int flags);
+int shep_get_rewards(shep_handle* h, void* dst, int flags);
+/* The three in one copy and one wait (the drop-in env's step): dst, host float64, holds
+ * the observation (B,N,4), then the adjacency (B,N,N), then the rewards (B). */
+int shep_get_outputs(shep_handle* h, double* dst);
+/* The control of the last step (B,N,2) host: shepherd rows u * action_scalar, sheep rows
+ * the repulsion (:89). */
+int shep_get_controls(shep_handle* h, double* dst);
+int shep_sync(shep_handle* h);
+
 /* Diagnostics ---------------------------------------------------------------- */
 const char* fe_last_error(void);
 int fe_abi_version(void);
