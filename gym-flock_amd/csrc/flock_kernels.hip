@@ -81,6 +81,10 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// The step kernel's `red` holds 8 doubles: [0,4) block_sum, [4,6) the float reductions
+// (redf), and in slot 6 an int flag: some agent of the env has a NaN coordinate.
+constexpr int kNanFlagSlot = 6;
+
 // State of agent `g` (flat index b*N + j) after the double-integrator update of
 // flocking_relative.py:96-105, in the reference's operation order. With a float32 u
 // the action terms are float32 arithmetic (NumPy keeps u*10.0, *dt, *0.5 in float32)
@@ -718,6 +722,10 @@ __device__ __forceinline__ void step_epilogue(const StepArgs& a, const St* tile,
 
   // every thread summed its share of the env's velocities while staging the tiles
   const double Svx = block_sum(svx, red), Svy = block_sum(svy, red);
+  // whether any agent of the env has a NaN coordinate (the centralised controller, below):
+  // the flag the staging threads set in LDS (kNanFlagSlot), published by the barriers above
+  [[maybe_unused]] bool anynan = false;
+  if constexpr (CTRL) anynan = *reinterpret_cast<const int*>(red + kNanFlagSlot) != 0;
 
   if (writer && !GF_ABLATE(a, 256)) {  // diag 256: skip the per-row outputs (timing only)
     const size_t g = env0 + i_row;
@@ -751,6 +759,24 @@ __device__ __forceinline__ void step_epilogue(const StepArgs& a, const St* tile,
         const bool frozen = i_row < nz;
         p2 = frozen ? 0.0 : static_cast<double>(N - nz) * me.vx - (Svx - zx);
         p3 = frozen ? 0.0 : static_cast<double>(N - nz) * me.vy - (Svy - zy);
+      }
+      if (a.centralized) {
+        // The centralised sum runs over ALL j, and the reference zeroes a pair's gradient only
+        // where r2 > comm_radius (:225): a pair whose r2 is NaN (a NaN coordinate, or inf - inf)
+        // keeps its NaN gradient, which the feature pass, visiting near pairs only, never
+        // sees. A finite row has such a pair iff some agent has a NaN coordinate; a row that
+        // is not finite itself (rare) looks at every other agent.
+        bool bad = anynan;
+        if (!__builtin_isfinite(me.px) || !__builtin_isfinite(me.py)) {
+          bad = false;
+          for (int j = 0; j < N && !bad; ++j) {
+            if (j == i_row) continue;
+            const St s = N <= T ? tile[j] : load_state<DYN, UF64, VAR>(a, env0 + j);
+            const double dx = me.px - s.px, dy = me.py - s.py;
+            bad = __builtin_isnan(dx * dx + dy * dy);
+          }
+        }
+        if (bad) gx = gy = __builtin_nan("");
       }
       double2 u;
       u.x = clip10(-gx - p2) / a.action_scalar;  // (-p4 - p2), :209-211
@@ -876,6 +902,12 @@ void flock_step_kernel(typename std::conditional<UIN, StepArgsU, StepArgs>::type
   double* red = reinterpret_cast<double*>(candb + (KN ? (size_t)R * Wt : 0));
   float* redf = reinterpret_cast<float*>(red + 4);
   float* inv = reinterpret_cast<float*>(red + 8);
+  // CTRL: set by the thread that stages an agent with a NaN coordinate (step_epilogue reads
+  // it); cleared here, before the first tile's barrier
+  [[maybe_unused]] int* nanflag = reinterpret_cast<int*>(red + kNanFlagSlot);
+  if constexpr (CTRL) {
+    if (threadIdx.x == 0) *nanflag = 0;
+  }
   [[maybe_unused]] float* rthr = inv + R;                      // R kNN candidate radii^2 (0: none)
   // each wave's copy of the rows' candidate bounds (read as LDS broadcasts)
   // and the block's predicted rows in order (prow[p]: the p-th predicted row)
@@ -1076,6 +1108,9 @@ void flock_step_kernel(typename std::conditional<UIN, StepArgsU, StepArgs>::type
       pt = fmaxf(pt, fmaxf(fabsf(fx), fabsf(fy)));
       svx += s.vx;
       svy += s.vy;
+      if constexpr (CTRL) {  // a store almost never taken: nothing more stays live in the pair loops
+        if (__builtin_isnan(s.px) || __builtin_isnan(s.py)) *nanflag = 1;
+      }
     };
     if constexpr (PF >= 1) {
 #pragma unroll
@@ -1856,7 +1891,10 @@ __global__ __launch_bounds__(kThreads) void flock_knn_kernel(KnnArgs a) {
 
 // get_stats (:136-143): vel_diffs_i = |v_i - mean v|, min_dists_i = sqrt(min_j r2_ij)
 // (r2 is exactly symmetric, so the reference's column min equals this row min), plus
-// the degree used by reset()'s acceptance test (:177-184).
+// the degree used by reset()'s acceptance test (:177-184). The minimum propagates NaN as
+// np.min does: a pair whose r2 is NaN (a NaN coordinate, or inf - inf) makes both agents'
+// min_dists NaN, so one agent with a NaN position makes every agent's NaN. The degree
+// never counts such a pair (NaN < cr2 is false, :117).
 __global__ __launch_bounds__(kThreads) void flock_stats_kernel(StatsArgs a) {
   __shared__ St tile[kTileMax];
   __shared__ double red[8];
@@ -1886,7 +1924,7 @@ __global__ __launch_bounds__(kThreads) void flock_stats_kernel(StatsArgs a) {
         const double dx = me.px - tile[t].px, dy = me.py - tile[t].py;
         const double r2 = dx * dx + dy * dy;
         const bool other = j0 + t != i;
-        if (other && r2 < mn) mn = r2;
+        if (other && (r2 < mn || r2 != r2)) mn = r2;  // a NaN r2 sticks: nothing is < NaN
         deg += (other && r2 < a.cr2) ? 1 : 0;
       }
     }

@@ -9,6 +9,8 @@ Variants and what they change against FlockingRelative-v0:
   stochastic  flocking_stoch.py: clip +-0.5, scale 6, dt ~ N(0.12, 0.018) per step
               (global RNG), controller clipped to +-0.5
   twoflocks   flocking_twoflocks.py: grid reset with opposing velocities
+variant_stochastic_inexact.npz is the stochastic env again with max_accel = 0.1 and
+scale = 0.3, neither exact in float32, and random actions of both dtypes.
 
 Each episode records the reset state and observation, then per step: the action, the
 state, state_values, adjacency bits/degree (the network is adj/deg), reward, and the
@@ -50,6 +52,25 @@ def _record(env, steps, u_fn, out):
         rec["dt"].append(env.dt)
     out.update({k: np.array(v) for k, v in rec.items()})
     return out
+
+
+def gen_stochastic_inexact(mod, cfg):
+    """stochastic, N=12, with a clip and a scale that float32 cannot represent
+    (max_accel = 0.1, scale = 0.3 set on the instance): 10 random steps, float32 and
+    float64 actions alternating, about two thirds of them beyond the clip. Same keys as
+    variant_stochastic.npz."""
+    np.random.seed(43)
+    env = mod.FlockingStochasticEnv()
+    env.params_from_cfg(_Cfg(n_agents=12, **cfg))
+    env.max_accel = 0.1
+    env.scale = 0.3
+    sv0, net0 = env.reset()
+    out = dict(seed=43, n_agents=12, x0=env.x.copy(), sv0=np.array(sv0))
+    rs = np.random.RandomState(8)
+    us = [rs.uniform(-0.3, 0.3, size=(12, 2)) for _ in range(10)]
+    out["u_is_f32"] = np.array([1, 0] * 5, np.int8)
+    _record(env, 10, lambda t, e: us[t].astype(np.float32) if t % 2 == 0 else us[t], out)
+    np.savez_compressed(os.path.join(OUT, "variant_stochastic_inexact.npz"), **out)
 
 
 def gen_variants():
@@ -94,6 +115,8 @@ def gen_variants():
     out["u_is_f32"] = np.array([0] * 20 + [1] * 5, np.int8)
     _record(env, 25, lambda t, e: e.controller() if t < 20 else u_f32[t - 20], out)
     np.savez_compressed(os.path.join(OUT, "variant_stochastic.npz"), **out)
+
+    gen_stochastic_inexact(mods["flocking_stoch"], cfg)
 
     # two flocks, N=20: grid reset with a global-RNG bias, 20 closed-loop steps
     np.random.seed(51)

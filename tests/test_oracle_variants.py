@@ -86,6 +86,26 @@ def test_stochastic_episode():
     replay("stochastic", x, f, dt_fn)
 
 
+def test_stochastic_inexact_episode(monkeypatch):
+    """The stochastic env with max_accel = 0.1 and scale = 0.3 (neither exact in
+    float32), float32 and float64 actions alternating, most of them beyond the clip."""
+    f = np.load(os.path.join(GOLDEN, "variant_stochastic_inexact.npz"))
+    n = int(f["n_agents"])
+    assert n == 12 and len(f["x"]) == 10 and f["u_is_f32"].tolist() == [1, 0] * 5
+    assert (np.abs(f["u"]) > 0.1).mean() > 0.5
+    monkeypatch.setitem(VARIANTS, "stochastic", dict(u_scale=0.3, u_clip=0.1, x_scale=0.3, ctrl_clip=0.1))
+    np.random.seed(int(f["seed"]))
+    x = fo.reset_rejection(n, r_max=np.sqrt(n))
+    np.testing.assert_array_equal(x, f["x0"])
+
+    def dt_fn(t):
+        dt = np.random.normal(0.12, 0.018)
+        assert dt == f["dt"][t]
+        return dt
+
+    replay("stochastic", x, f, dt_fn)
+
+
 def test_twoflocks_episode():
     f = np.load(os.path.join(GOLDEN, "variant_twoflocks.npz"))
     n = int(f["n_agents"])
