@@ -23,6 +23,7 @@
 #include "device_alloc.h"
 #include "flock_internal.h"
 #include "gymflock.h"
+#include "mt19937.h"
 
 namespace {
 
@@ -206,6 +207,16 @@ struct fe_handle {
     bool live = false;
     unsigned bmask = 0;                       // bits buffers it reads
   } kread[2];                                 // by the state buffer x[i] the kNN reads
+  // fe_reset_device / fe_set_rng: the envs' MT19937 streams and the reset's outputs,
+  // allocated on first use (ensure_rng)
+  uint32_t* rng_key = nullptr;                // (B,624)
+  int32_t* rng_pos = nullptr;                 // (B)
+  int32_t* reset_tries = nullptr;             // (B)
+  uint8_t* reset_status = nullptr;            // (B)
+  int32_t* reset_envs = nullptr;              // (B) the selected envs of a masked reset
+  int32_t* reset_envs_host = nullptr;         // (B) page-locked: the list's upload reads it
+  hipEvent_t ev_envs = nullptr;               // that upload (before the list is rewritten)
+  std::vector<uint8_t> rng_set;               // (B) the env's stream was seeded or set
 };
 
 namespace {
@@ -460,6 +471,11 @@ void release(fe_handle* h) {
     if (p) hipFree(p);
   if (h->fin_cnt) hipFree(h->fin_cnt);
   if (h->fin_host) hipHostFree(h->fin_host);
+  for (void* p : {(void*)h->rng_key, (void*)h->rng_pos, (void*)h->reset_tries, (void*)h->reset_status,
+                  (void*)h->reset_envs})
+    if (p) hipFree(p);
+  if (h->reset_envs_host) hipHostFree(h->reset_envs_host);
+  if (h->ev_envs) hipEventDestroy(h->ev_envs);
   if (h->stage_done) hipHostFree(h->stage_done);  // (the side stream drained or was never used)
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
   if (h->h2d_ev) hipEventDestroy(h->h2d_ev);
@@ -1017,6 +1033,143 @@ int fe_get_state_env(fe_handle* h, int env, double* x) {
   if (int rc = use_dev(h)) return rc;
   const size_t n = (size_t)h->cfg.n_agents * 4;
   return d2h(h, x, h->x[h->cur] + env * n, n * sizeof(double));
+}
+
+}  // extern "C"
+
+namespace {
+// The envs' stream buffers and the device reset's outputs, on first use (zeroed).
+int ensure_rng(fe_handle* h) {
+  if (h->rng_key) return GF_OK;
+  const size_t B = h->cfg.n_envs;
+  int rc;
+  if ((rc = dalloc(&h->rng_key, B * gf::kMtN)) || (rc = dalloc(&h->rng_pos, B)) || (rc = dalloc(&h->reset_tries, B)) ||
+      (rc = dalloc(&h->reset_status, B)) || (rc = dalloc(&h->reset_envs, B)))
+    return rc;
+  GF_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->reset_envs_host), B * sizeof(int32_t), hipHostMallocDefault));
+  GF_HIP(hipEventCreateWithFlags(&h->ev_envs, hipEventDisableTiming));
+  GF_HIP(hipMemsetAsync(h->rng_key, 0, B * gf::kMtN * sizeof(uint32_t), h->stream));
+  GF_HIP(hipMemsetAsync(h->rng_pos, 0, B * sizeof(int32_t), h->stream));
+  GF_HIP(hipMemsetAsync(h->reset_tries, 0, B * sizeof(int32_t), h->stream));
+  GF_HIP(hipMemsetAsync(h->reset_status, 0, B, h->stream));
+  h->rng_set.assign(B, 0);
+  return GF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fe_reset_device(fe_handle* h, const fe_reset_config* rc, uint64_t seed, const uint8_t* env_mask, int flags,
+                    int32_t* tries, uint8_t* status) {
+  if (!h || !rc) return fail(GF_EINVAL, "null argument");
+  if (flags & ~(FE_RESET_SEED | FE_RESET_NO_REJECT)) return fail(GF_EINVAL, "fe_reset_device: unknown flag");
+  const int N = h->cfg.n_agents, B = h->cfg.n_envs;
+  const bool seeded = flags & FE_RESET_SEED, reject = !(flags & FE_RESET_NO_REJECT);
+  if (rc->max_tries < 1 || rc->max_tries > gf::kResetMaxTries)
+    return fail(GF_EINVAL, "fe_reset_device: max_tries must be in [1, 65536]");
+  if (!(rc->r_max >= 0) || !std::isfinite(rc->r_max) || !std::isfinite(rc->v_max) || !std::isfinite(rc->v_bias) ||
+      !std::isfinite(rc->min_dist))
+    return fail(GF_EINVAL, "fe_reset_device: r_max must be >= 0 and r_max, v_max, v_bias, min_dist finite");
+  if (reject && N > gf::kResetMaxN)
+    return fail(GF_EINVAL, "fe_reset_device: the rejection sampler holds a candidate in LDS, n_agents <= 1024 "
+                           "(FE_RESET_NO_REJECT takes any size)");
+  if (seeded && seed + (uint64_t)B > 0x100000000ull) return fail(GF_EINVAL, "seed + n_envs must fit in 32 bits");
+  std::vector<int32_t> sel;
+  if (env_mask) {
+    for (int b = 0; b < B; ++b)
+      if (env_mask[b]) sel.push_back(b);
+    if (sel.empty()) {  // nothing to do: the outputs are those of the envs' last resets
+      if (!tries && !status) return GF_OK;
+      if (!h->rng_key) {
+        if (tries) std::fill(tries, tries + B, 0);
+        if (status) std::fill(status, status + B, 0);
+        return GF_OK;
+      }
+      if (int r = use_dev(h)) return r;
+      if (tries) GF_HIP(hipMemcpyAsync(tries, h->reset_tries, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+      if (status) GF_HIP(hipMemcpyAsync(status, h->reset_status, (size_t)B, hipMemcpyDeviceToHost, h->stream));
+      GF_HIP(hipStreamSynchronize(h->stream));
+      return GF_OK;
+    }
+  }
+  const int n_sel = env_mask ? static_cast<int>(sel.size()) : B;
+  if (!seeded) {
+    bool all_set = !h->rng_set.empty();
+    for (int k = 0; all_set && k < n_sel; ++k) all_set = h->rng_set[env_mask ? sel[k] : k] != 0;
+    if (!all_set)
+      return fail(GF_ESTATE, "fe_reset_device: a selected env's stream was never seeded or set (FE_RESET_SEED or fe_set_rng)");
+  }
+  if (int r = use_dev(h)) return r;
+  if (int r = ensure_rng(h)) return r;
+  gf::ResetArgs a{};
+  a.n_sel = n_sel;
+  a.envs = nullptr;
+  if (env_mask && n_sel < B) {
+    GF_HIP(hipEventSynchronize(h->ev_envs));  // the previous list's upload has read the host copy
+    std::copy(sel.begin(), sel.end(), h->reset_envs_host);
+    GF_HIP(hipMemcpyAsync(h->reset_envs, h->reset_envs_host, sel.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                          h->stream));
+    GF_HIP(hipEventRecord(h->ev_envs, h->stream));
+    a.envs = h->reset_envs;
+  }
+  a.N = N;
+  a.reject = reject ? 1 : 0;
+  a.seeded = seeded ? 1 : 0;
+  a.seed0 = static_cast<uint32_t>(seed);
+  a.r_max = rc->r_max;
+  a.v_max = rc->v_max;
+  a.v_bias = rc->v_bias;
+  a.min_dist = rc->min_dist;
+  a.cr2 = h->cfg.comm_radius * h->cfg.comm_radius;  // self.comm_radius2 (:43)
+  a.min_degree = rc->min_degree;
+  a.max_tries = rc->max_tries;
+  a.x = h->x[h->cur];
+  a.mt_key = h->rng_key;
+  a.mt_pos = h->rng_pos;
+  a.tries = h->reset_tries;
+  a.status = h->reset_status;
+  if (hipError_t e = gf::launch_reset(a, h->stream); e != hipSuccess) return fail_hip("flock_reset_kernel", e);
+  for (int k = 0; k < n_sel; ++k) h->rng_set[env_mask ? sel[k] : k] = 1;
+  GF_HIP(clear_knn_history(h));
+  h->has_state = true;
+  h->has_ctrl = h->has_obs = h->has_knn = false;
+  if (tries) GF_HIP(hipMemcpyAsync(tries, h->reset_tries, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (status) GF_HIP(hipMemcpyAsync(status, h->reset_status, (size_t)B, hipMemcpyDeviceToHost, h->stream));
+  if (tries || status) GF_HIP(hipStreamSynchronize(h->stream));
+  return GF_OK;
+}
+
+int fe_set_rng(fe_handle* h, int env, const uint32_t* keys, const int32_t* pos) {
+  if (!h || !keys || !pos || env < -1) return fail(GF_EINVAL, "bad argument");
+  if (env >= 0)
+    if (int rc = check_env(h, env)) return rc;
+  const size_t n = env < 0 ? h->cfg.n_envs : 1, first = env < 0 ? 0 : env;
+  for (size_t k = 0; k < n; ++k)
+    if (pos[k] < 0 || pos[k] > gf::kMtN) return fail(GF_EINVAL, "stream position outside [0, 624]");
+  if (int rc = use_dev(h)) return rc;
+  if (int rc = ensure_rng(h)) return rc;
+  GF_HIP(hipMemcpyAsync(h->rng_key + first * gf::kMtN, keys, n * gf::kMtN * sizeof(uint32_t), hipMemcpyHostToDevice,
+                        h->stream));
+  GF_HIP(hipMemcpyAsync(h->rng_pos + first, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
+  for (size_t k = 0; k < n; ++k) h->rng_set[first + k] = 1;
+  return GF_OK;
+}
+
+int fe_get_rng(fe_handle* h, int env, uint32_t* keys, int32_t* pos) {
+  if (!h || !keys || !pos || env < -1) return fail(GF_EINVAL, "bad argument");
+  if (env >= 0)
+    if (int rc = check_env(h, env)) return rc;
+  const size_t n = env < 0 ? h->cfg.n_envs : 1, first = env < 0 ? 0 : env;
+  for (size_t k = 0; k < n; ++k)
+    if (h->rng_set.empty() || !h->rng_set[first + k])
+      return fail(GF_ESTATE, "fe_get_rng: the env's stream was never seeded or set (fe_reset_device, fe_set_rng)");
+  if (int rc = use_dev(h)) return rc;
+  GF_HIP(hipMemcpyAsync(keys, h->rng_key + first * gf::kMtN, n * gf::kMtN * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                        h->stream));
+  GF_HIP(hipMemcpyAsync(pos, h->rng_pos + first, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
+  return GF_OK;
 }
 
 int fe_compute_helpers(fe_handle* h, int flags) {
@@ -2204,3 +2357,10 @@ int fe_runtime_info(int32_t* hip_runtime_version, int32_t* hip_driver_version, i
 }
 
 }  // extern "C"
+
+// flock_reset.hip is a source of its own in this directory's Makefile (GF_RESET_OWN_TU). A
+// build that lists the library's sources without it (the host-sanitizer build of the
+// C-ABI, tests/asan) gets its kernel and launcher here, with this file's flags.
+#ifndef GF_RESET_OWN_TU
+#include "flock_reset.hip"
+#endif

@@ -139,6 +139,30 @@ struct StatsArgs {
   int N, B;
 };
 
+// reset() on the device (flock_reset.hip; flocking_relative.py:156-192): one workgroup per
+// selected env draws candidates from the env's MT19937 stream until one passes the
+// reference's acceptance test, at most max_tries of them.
+constexpr int kResetMaxN = 1024;        // rejection mode: positions and velocities in LDS
+constexpr int kResetMaxTries = 65536;
+struct ResetArgs {
+  int n_sel;
+  const int32_t* envs;    // (n_sel) env of each workgroup, or nullptr: envs 0..n_sel-1
+  int N;
+  int reject;             // 0: keep the first draw, no pair test (the synthetic init)
+  int seeded;             // stream b := RandomState(seed0 + b) first; else continued
+  uint32_t seed0;
+  double r_max, v_max, v_bias;
+  double min_dist, cr2;   // cr2: comm_radius * comm_radius as the host rounds it
+  int min_degree, max_tries;
+  double* x;              // (B,N,4) the state buffer written (selected envs only)
+  uint32_t* mt_key;       // (B,624) each env's stream
+  int32_t* mt_pos;        // (B) in [0, 624]
+  int32_t* tries;         // (B) out: candidates drawn
+  uint8_t* status;        // (B) out: FE_RESET_EXHAUSTED
+};
+size_t reset_lds_bytes(int N, bool reject);
+hipError_t launch_reset(const ResetArgs& a, hipStream_t s);
+
 // Launch-geometry helpers shared by host and tests.
 int step_rows_per_block(int N);
 int step_tile(int N);

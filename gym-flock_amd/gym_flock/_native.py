@@ -28,6 +28,9 @@ FE_NO_STATE_VALUES = 0x40
 FE_U_RESIDENT = 0x80
 FE_PACKED_NETWORK = 0x100
 FE_OUT_MAPPED = 0x1  # fe_get_outputs flag
+FE_RESET_SEED = 0x1  # fe_reset_device flags
+FE_RESET_NO_REJECT = 0x2
+FE_RESET_EXHAUSTED = 0x1  # fe_reset_device status bit
 
 
 class FeConfig(ctypes.Structure):
@@ -50,6 +53,12 @@ class FeVariant(ctypes.Structure):
     _fields_ = [("n_frozen", ctypes.c_int32), ("n_vel_zero", ctypes.c_int32),
                 ("u_scale", ctypes.c_double), ("u_clip", ctypes.c_double),
                 ("x_scale", ctypes.c_double), ("ctrl_clip", ctypes.c_double)]
+
+
+class FeResetConfig(ctypes.Structure):
+    _fields_ = [("r_max", ctypes.c_double), ("v_max", ctypes.c_double), ("v_bias", ctypes.c_double),
+                ("min_dist", ctypes.c_double), ("min_degree", ctypes.c_int32),
+                ("max_tries", ctypes.c_int32)]
 
 
 class CovConfig(ctypes.Structure):
@@ -172,6 +181,9 @@ SIGNATURES = {
     "fe_get_network_rows": [_P, _I, _I, _I, _P],
     "fe_get_network_packed": [_P, _I, _P, _P],
     "fe_reset_synthetic": [_P, ctypes.c_uint64, ctypes.c_double],
+    "fe_reset_device": [_P, ctypes.POINTER(FeResetConfig), ctypes.c_uint64, _P, _I, _P, _P],
+    "fe_set_rng": [_P, _I, _P, _P],
+    "fe_get_rng": [_P, _I, _P, _P],
     "fe_get_controls": [_P, _I, _P],
     "fe_get_rewards": [_P, _P],
     "fe_get_outputs": [_P, _I, _P, _P, _P, _I],
@@ -524,6 +536,59 @@ class FlockHandle:
     def reset_synthetic(self, seed=0, v_max=5.0):
         """Synthetic init of every env in the library (fe_reset_synthetic)."""
         check(self.lib.fe_reset_synthetic(self.h, int(seed), float(v_max)))
+
+    def reset_device(self, seed=None, envs=None, reject=True, max_tries=4096, r_max=None, v_max=5.0,
+                     v_bias=None, min_dist=0.1, min_degree=2, fetch=True):
+        """reset() (flocking_relative.py:156-192) of the selected envs in one launch
+        (fe_reset_device): each env's rejection sampler on its own MT19937 stream, seeded
+        RandomState(seed + b) or, with seed None, continued. envs: None (all), a bool mask
+        (B) or a list of env indices. reject=False keeps the first draw (the synthetic
+        init). r_max defaults to sqrt(N) (params_from_cfg), v_bias to v_max. Returns
+        (tries (B) int32, status (B) uint8) of every env, the unselected ones' from their
+        last reset; fetch=False only enqueues and returns None."""
+        n = self.n_envs
+        mask = None
+        if envs is not None:
+            e = np.asarray(envs)
+            if e.dtype == np.bool_:
+                assert e.shape == (n,), e.shape
+                mask = np.ascontiguousarray(e, dtype=np.uint8)
+            else:
+                mask = np.zeros(n, np.uint8)
+                mask[e.astype(np.int64)] = 1
+        rc = FeResetConfig(float(math.sqrt(self.n_agents) if r_max is None else r_max), float(v_max),
+                           float(v_max if v_bias is None else v_bias), float(min_dist), int(min_degree),
+                           int(max_tries))
+        flags = (0 if seed is None else FE_RESET_SEED) | (0 if reject else FE_RESET_NO_REJECT)
+        tries = np.empty(n, np.int32) if fetch else None
+        status = np.empty(n, np.uint8) if fetch else None
+        check(self.lib.fe_reset_device(self.h, ctypes.byref(rc), int(seed or 0), ptr(mask), flags,
+                                       ptr(tries), ptr(status)))
+        return (tries, status) if fetch else None
+
+    def set_rng(self, states, env=None):
+        """The envs' MT19937 streams for reset_device(seed=None): a list of B RandomState
+        objects or get_state() tuples (the legacy np.random state), or one with env=<b>
+        (fe_set_rng)."""
+        if env is not None:
+            states = [states]
+        assert len(states) == (self.n_envs if env is None else 1)
+        keys = np.empty((len(states), 624), np.uint32)
+        pos = np.empty(len(states), np.int32)
+        for b, st in enumerate(states):
+            st = st.get_state() if hasattr(st, "get_state") else st
+            assert st[0] == "MT19937" and len(st[1]) == 624, "a legacy RandomState (MT19937) state"
+            keys[b], pos[b] = st[1], st[2]
+        check(self.lib.fe_set_rng(self.h, -1 if env is None else int(env), ptr(keys), ptr(pos)))
+
+    def get_rng(self, env=None):
+        """(keys (B,624) uint32, pos (B) int32) of every env's stream, or (keys (624), pos)
+        of one: RandomState.set_state(("MT19937", keys, pos)) continues it (fe_get_rng)."""
+        n = self.n_envs if env is None else 1
+        keys = np.empty((n, 624), np.uint32)
+        pos = np.empty(n, np.int32)
+        check(self.lib.fe_get_rng(self.h, -1 if env is None else int(env), ptr(keys), ptr(pos)))
+        return (keys, pos) if env is None else (keys[0], int(pos[0]))
 
     def set_state(self, x, env=None):
         x = np.ascontiguousarray(x, dtype=np.float64)

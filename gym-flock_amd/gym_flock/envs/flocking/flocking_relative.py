@@ -19,6 +19,10 @@ Differences a caller can observe:
     seeded runs reproduce the reference bit for bit) up to `reset_max_attempts`
     draws, then falls back to a single draw (the reference would loop forever,
     SURVEY.md finding 5); `reset_mode='synthetic'` skips the rejection.
+    `reset_mode='device'` runs the same sampler in one launch on the global np.random
+    stream (fe_reset_device): same uniforms, velocities and acceptances and the same
+    np.random state afterwards, positions with the device's cos / sin (relative
+    difference below 2e-15 from NumPy's).
 """
 import warnings
 
@@ -301,8 +305,34 @@ class FlockingRelativeEnv(Env):
         _, min_dists, deg = h.stats(0)
         return deg.min() >= 2 and min_dists.min() >= 0.1
 
+    _NO_DRAW_WARNING = ("FlockingRelativeEnv.reset(): no draw met the reference's acceptance test "
+                        "(min degree >= 2, min distance >= 0.1) in %d attempts; keeping the last one")
+
+    def _reset_device(self):
+        """:156-192 in one launch: the global np.random stream goes to the handle, the
+        device draws and tests up to reset_max_attempts candidates from it, and np.random
+        gets the stream back where the reference's loop would have left it (a pending
+        cached gaussian is not part of the uniform stream and stays as it was)."""
+        h = self._handle()
+        st = np.random.get_state()
+        h.set_rng(st[:3], env=0)
+        _, status = h.reset_device(None, None, True, self.reset_max_attempts, self.r_max, self.v_max,
+                                   self.v_bias)
+        key, pos = h.get_rng(0)
+        np.random.set_state((st[0], key, pos, st[3], st[4]))
+        if status[0] & nat.FE_RESET_EXHAUSTED:
+            warnings.warn(self._NO_DRAW_WARNING % self.reset_max_attempts, RuntimeWarning, stacklevel=3)
+        x = h.get_state(0)
+        self.mean_vel = np.mean(x[:, 2:4], axis=0)
+        self.init_vel = x[:, 2:4]
+        self._invalidate()
+        self.compute_helpers()
+        return (self.state_values, self.state_network)
+
     def reset(self):
         """:156-192."""
+        if self.reset_mode == "device":
+            return self._reset_device()
         x = None
         for _ in range(self.reset_max_attempts if self.reset_mode == "reference" else 1):
             x = draw_swarm(self.n_agents, self.r_max, self.v_max, self.v_bias)
@@ -311,9 +341,7 @@ class FlockingRelativeEnv(Env):
         else:
             # the reference loops until a draw passes (flocking_relative.py:164), which
             # never ends for N >~ 200; this keeps the last draw instead, and says so
-            warnings.warn("FlockingRelativeEnv.reset(): no draw met the reference's acceptance test "
-                          "(min degree >= 2, min distance >= 0.1) in %d attempts; keeping the last one"
-                          % self.reset_max_attempts, RuntimeWarning, stacklevel=2)
+            warnings.warn(self._NO_DRAW_WARNING % self.reset_max_attempts, RuntimeWarning, stacklevel=2)
         self.mean_vel = np.mean(x[:, 2:4], axis=0)
         self.init_vel = x[:, 2:4]
         self.x = x

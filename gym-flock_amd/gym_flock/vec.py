@@ -51,6 +51,29 @@ class VecFlockingRelative:
         self.h.compute_helpers()
         return x
 
+    def reset_device(self, seed=None, envs=None, reject=True, max_tries=4096, r_max=None, fetch=True):
+        """reset() of the reference (flocking_relative.py:156-192) on the device, one launch
+        for the selected envs: env b draws from its own stream, RandomState(seed + env_offset
+        + b) or, with seed None, continued where its last reset left it, until a draw passes
+        the reference's acceptance test (min degree >= 2, min distance >= 0.1) or max_tries
+        are spent (the last draw is kept; status bit FE_RESET_EXHAUSTED). envs: None (all),
+        a bool mask or an index list; the other envs keep state and stream, so a trainer
+        resets the envs whose episode ended between two steps. reject=False keeps the first
+        draw (reset()'s synthetic init, any N). r_max: the reference's self.r_max, sqrt(N)
+        by default. Ends with compute_helpers(). Returns (tries, status) per env, or None
+        with fetch=False (nothing waits for the device then)."""
+        s = None if seed is None else int(seed) + self.env_offset
+        out = self.h.reset_device(s, envs, reject, max_tries, r_max, self.v_max, fetch=fetch)
+        self.h.compute_helpers()
+        return out
+
+    def np_random(self, env):
+        """A RandomState at env `env`'s device stream position (after its last reset)."""
+        keys, pos = self.h.get_rng(env)
+        rs = np.random.RandomState()
+        rs.set_state(("MT19937", keys, pos))
+        return rs
+
     def set_state(self, x):
         self.h.set_state(x)
 

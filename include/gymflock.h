@@ -137,6 +137,43 @@ int fe_reset_synthetic(fe_handle* h, uint64_t seed, double v_max);
 int fe_get_state(fe_handle* h, double* x);                  /* env.x (B,N,4) */
 int fe_get_state_env(fe_handle* h, int env, double* x);     /* one env's (N,4) */
 
+/* reset() on the device (flocking_relative.py:156-192): the rejection sampler of every
+ * selected env in one launch, one workgroup per env, each drawing from its env's own
+ * MT19937 stream (numpy's legacy RandomState) in the reference's order: length[N],
+ * angle[N], bias[2], vx[N], vy[N], 4N+2 doubles per candidate whether it is accepted or
+ * not. The uniforms, lengths, angles and velocities are NumPy's bit for bit; positions
+ * use the device's double cos / sin (relative difference below 2e-15). A candidate is
+ * accepted as :176-184 decide: min over i != j of a_ij = dx*dx + dy*dy has sqrt >=
+ * min_dist, and every agent has at least min_degree others with a_ij < comm_radius *
+ * comm_radius (the handle's comm_radius, the product rounded on the host). */
+typedef struct fe_reset_config {
+  double r_max, v_max, v_bias;   /* :167-174; r_max is the reference's self.r_max (sqrt(N) after params_from_cfg) */
+  double min_dist;               /* 0.1 (:160) */
+  int32_t min_degree;            /* 2   (:164) */
+  int32_t max_tries;             /* 1..65536 */
+} fe_reset_config;
+#define FE_RESET_SEED      0x1   /* seed env b's stream as RandomState(seed + b) first; else continue it */
+#define FE_RESET_NO_REJECT 0x2   /* keep the first draw (the synthetic init) */
+#define FE_RESET_EXHAUSTED 0x1   /* status bit: no try was accepted, the last one kept */
+/* env_mask: (B) bytes, nonzero = reset this env, or NULL = all; the other envs keep their
+ * state, stream, tries and status (a mask selecting none: nothing happens, GF_OK). tries
+ * and status: (B) host arrays or NULL. With both NULL the call only enqueues the launch on
+ * the handle's stream (after both halves of the latest step); otherwise it waits and
+ * copies. An env whose max_tries candidates were all rejected keeps the last one
+ * (FE_RESET_EXHAUSTED in its status); its stream stands after max_tries candidates.
+ * Afterwards the handle is as after fe_set_state_env: the caller runs fe_compute_helpers
+ * (reset() :191). The rejection mode holds a candidate in LDS: n_agents <= 1024 (nothing
+ * above roughly 150 agents is ever accepted), GF_EINVAL beyond; FE_RESET_NO_REJECT takes
+ * any n_agents. GF_ESTATE without FE_RESET_SEED for an env whose stream was never seeded
+ * or set; GF_EINVAL unless seed + n_envs fits in 32 bits. The stream buffers are allocated
+ * by the first fe_reset_device / fe_set_rng call of a handle. */
+int fe_reset_device(fe_handle* h, const fe_reset_config* rc, uint64_t seed, const uint8_t* env_mask /* (B) or NULL = all */,
+                    int flags, int32_t* tries /* (B) host or NULL */, uint8_t* status /* (B) host or NULL */);
+/* The envs' streams as RandomState.get_state() has them: keys (624 words each) and
+ * positions in [0, 624]. env = -1: all envs, keys (B,624) and pos (B); else one env's. */
+int fe_set_rng(fe_handle* h, int env /* -1 = all */, const uint32_t* keys /* (.,624) */, const int32_t* pos);
+int fe_get_rng(fe_handle* h, int env, uint32_t* keys, int32_t* pos);
+
 /* Hot path ------------------------------------------------------------------- */
 /* Upload (B,N,2) actions (float32, or float64 if f64) into the handle's resident
  * action buffer, used by fe_step(..., FE_U_RESIDENT). */
