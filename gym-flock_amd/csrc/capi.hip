@@ -1,223 +1,24 @@
 // C-ABI of libgymflock.so (include/gymflock.h): handle lifecycle, device buffers,
-// stream-ordered launches, host transfers, RCCL metrics path and error reporting.
-#include <rccl/rccl.h>
-
-#include <dlfcn.h>
-
+// stream-ordered launches, host transfers and error reporting. The RCCL metrics path is
+// flock_comm.hip; the two meet in flock_handle.h.
 #include <algorithm>
-#include <chrono>
-#include <atomic>
-#include <condition_variable>
-#include <deque>
-#include <memory>
-#include <mutex>
-#include <cstdio>
-#include <cstdlib>
 #include <cmath>
-#include <cstring>
 #include <random>
 #include <string>
-#include <thread>
 #include <vector>
 
-#include "device_alloc.h"
-#include "flock_internal.h"
-#include "gymflock.h"
+#include "flock_handle.h"
 #include "mt19937.h"
 
-namespace {
+using namespace gf;  // capi_common.h's helpers and flock_handle.h's internal calls
 
-thread_local std::string g_err;
+// One thread-local error message for every C-ABI file (capi_common.h).
+static thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
+int gf::set_error(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-
-int fail_hip(const char* what, hipError_t e) {
-  return fail(GF_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define GF_HIP(expr)                                        \
-  do {                                                      \
-    hipError_t e_ = (expr);                                 \
-    if (e_ != hipSuccess) return fail_hip(#expr, e_);       \
-  } while (0)
-
-// Reward ring: the t-th reward-writing launch writes slot t % kRewardSlots. The metrics
-// all-gather ships every step written since the previous gather (at most kRewardSlots).
-constexpr int kRewardSlots = 64;
-// fe_comm_init's bound on the communicator's creation, its shard-size exchange and every
-// later wait for a collective
-constexpr double kCommInitTimeoutS = 300.0;
-
-}  // namespace
-
-namespace gf {
-// Shared with the Coverage C-ABI (cov_capi.hip): one thread-local error message.
-int set_error(int code, const std::string& msg) { return fail(code, msg); }
-}  // namespace gf
-
-struct fe_handle {
-  fe_config cfg{};
-  hipStream_t stream = nullptr;
-  hipStream_t comm_stream = nullptr;
-  // Split steps: the step's env batch goes out as two launches, envs [0, B0) on
-  // `stream` and [B0, B) on `stream2`, so one launch's ramp and tail overlap the other's
-  // body (175.8 vs 196.0 us per config-2 step). The halves only depend on
-  // their own previous step; `stream` waits for `stream2` (join) before any other work.
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ev_s2 = nullptr;           // stream2 -> stream join
-  hipEvent_t ev_main = nullptr;         // stream -> stream2 ordering
-  int nsplit = 2;                       // launches per step (fe_set_streams)
-  bool s2_pending = false;              // stream2 holds work `stream` has not waited for
-  bool main_dirty = true;               // `stream` holds work stream2 has not waited for
-  bool dephase = true;                  // the next split step starts the halves apart (other
-                                        // work or a single launch came before it)
-  bool other_work = true;               // non-step work was enqueued since the last step:
-                                        // the next step goes out as one launch (a split
-                                        // step would only wait on it across streams)
-  hipEvent_t tw[2] = {nullptr, nullptr};  // split-step timing window (fe_kernel_timing)
-  int64_t tw_steps = 0;
-  double* x[2] = {nullptr, nullptr};
-  int cur = 0;
-  void* u = nullptr;                    // (B,N,2) up to float64
-  double* ctrl[2] = {nullptr, nullptr};
-  int ccur = 0;
-  float* sv = nullptr;
-  float* net = nullptr;
-  double* reward_ring = nullptr;        // kRewardSlots x B
-  int rslot = 0;
-  int64_t steps_written = 0;            // reward-writing launches so far (slot = count % slots)
-  // kNN outputs, one pair per state buffer: knn_idx[i] / knn_obs[i] belong to x[i], so
-  // a fused step (which writes those of its output state) never overlaps the rim kNN of
-  // the previous state, and the kread events that guard x[i] guard them too
-  int32_t* knn_idx[2] = {nullptr, nullptr};
-  float* knn_obs[2] = {nullptr, nullptr};
-  // each ranked row's k-th nearest r2 (0: unknown), by state buffer: a fused step reads
-  // the one of two states back (complete: the step waits for that state's kNN) to pick
-  // the rows it ranks beyond their neighbours, and writes its own
-  float* knn_r2[2] = {nullptr, nullptr};
-  uint8_t* knn_rimflag[2] = {nullptr, nullptr};  // per state buffer: blocks with rim rows
-  double* vel_diffs = nullptr;
-  double* min_dists = nullptr;
-  int32_t* degree = nullptr;
-  int u_resident_f64 = -1;              // dtype of the resident actions (-1: none)
-  bool has_state = false, has_ctrl = false, has_obs = false, has_knn = false;
-  bool obs_on_host = false;             // the last launch wrote state_values / network to
-                                        // host arrays only (fe_step_host): device copies stale
-  int R = 0, T = 0, bpe = 0;
-  int knn_exact = 0;                    // the fused kNN is exact in the step (gf::step_knn_exact)
-  size_t BN = 0;
-  int diag = 0;                         // ablation switches (diagnostic build only, fe_diag)
-  int prefetch = 0;                     // tile loads one tile ahead (N >= 16 tiles)
-  int store_fast[2] = {0, 1};           // fast network store loop: plain step / with controller
-  // kernel timing (bench roofline)
-  bool timing = false;
-  int timing_stride = 1;                // sample every timing_stride-th launch
-  int64_t timing_count = 0;
-  std::vector<hipEvent_t> ev;
-  size_t ev_used = 0;
-  // RCCL metrics path. Shards may differ in size: every gathered block is padded to the
-  // largest shard (max_envs), rank r's entries past its n_envs are zero.
-  ncclComm_t comm = nullptr;
-  int nranks = 1, rank = 0;
-  int max_envs = 0;
-  std::vector<int32_t> shard_sizes;     // every rank's n_envs (fe_comm_init's exchange)
-  double comm_timeout = kCommInitTimeoutS;  // bound on every wait for a collective
-  // The step streams never wait on the side stream on the device: a collective stuck on
-  // a dead peer (and, through it, everything queued behind it) must not stall the steps.
-  // A step about to overwrite a ring slot that a gather's staging copy has not read yet
-  // waits for that copy on the host, bounded by comm_timeout (next_reward_slot); normally
-  // the copy finished long before (the slot was written kRewardSlots steps ago).
-  double* gsend = nullptr;              // kRewardSlots x max_envs: the gathered steps, padded
-  std::string comm_lost;                // why the metrics path was torn down (a timed-out wait)
-  double* gather = nullptr;             // nranks x kRewardSlots x max_envs
-  hipEvent_t step_ev = nullptr;
-  hipEvent_t step_ev2 = nullptr;        // the gather's wait on stream2 (split steps)
-  hipEvent_t h2d_ev = nullptr;          // completion of the borrowed host-action copy
-  // Host actions of split steps (fe_step without FE_U_*): copied on a stream of their own
-  // into one of two device buffers, so the copy for step t+1 runs while step t computes;
-  // buffer k is rewritten only after both halves of the step that read it (two calls
-  // back) have finished (ev_uread), and both halves of its step wait for its copy.
-  hipStream_t ustream = nullptr;
-  void* ubuf[2] = {nullptr, nullptr};   // (B,N,2) up to float64 each
-  hipEvent_t ev_ucopy[2] = {nullptr, nullptr};
-  hipEvent_t ev_uread[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-  bool uread_live[2] = {false, false};
-  int ucur = 0;
-  // ring slots a reward gather's staging copy still reads: steps [first, ...) until the
-  // copy kernel (on the side stream) has stored `seq` into completion word kWordRing
-  struct RingRead {
-    int64_t first;
-    uint32_t seq;
-  };
-  std::deque<RingRead> ring_reads;
-  // The side stream's completion words (kWord*): page-locked (mapped, coherent), each
-  // stored by a kernel on the side stream with a system-scope release once the work
-  // before it is done, and polled by the host instead of querying events; never freed
-  // once a communicator was aborted (an abandoned kernel may still store into them)
-  uint32_t* stage_done = nullptr;
-  uint32_t* stage_done_dev = nullptr;
-  uint32_t stage_seq[4] = {0, 0, 0, 0};  // the last sequence number issued per word
-  int64_t gathered_upto = 0;            // steps before this one were shipped (or skipped)
-  bool ag_issued = false;
-  int last_count = 0;
-  double* stats_sum = nullptr;          // (B,2) get_stats means per env (fe_stats_summary)
-  double* ssend = nullptr;              // (max_envs,2) the stats gather's padded send block
-  double* stats_gather = nullptr;       // nranks x max_envs x 2 (fe_allgather_stats)
-  bool sg_pending = false;
-  // fe_debug_comm_gate: a bounded spin kernel on comm_stream, released by this page-locked
-  // flag, stands in for a collective whose peer stopped responding (tests only)
-  unsigned* gate_flag = nullptr;
-  // fe_debug_comm_state: what the ring-slot reuse and the gathers saw (tests only)
-  int32_t dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // fe_step_host*: the launch's completion flag (done_flag.h), allocated on first use: the
-  // device counter, the page-locked word and its mapped address
-  int32_t* fin_cnt = nullptr;
-  int32_t* fin_host = nullptr;
-  int32_t* fin_dev = nullptr;
-  int32_t fin_seq = 0;
-  // flocking variant (fe_set_variant / fe_set_dt)
-  bool has_variant = false;
-  fe_variant var{};
-  double* dt_env = nullptr;             // (B) per-env dt
-  bool dt_per_env = false;
-  // packed output mode (FE_PACKED_NETWORK) and the kNN step's adjacency: two buffers,
-  // so a step can write one while the kNN of the previous step reads the other
-  uint64_t* adj_bits[2] = {nullptr, nullptr};  // (B,N,Wn)
-  int32_t* pdeg[2] = {nullptr, nullptr};       // (B,N)
-  int bits_cur = 0;                     // buffer of the latest bits / degrees
-  bool has_packed = false;
-  // Flocking-v0 pipelining: the kNN of step t runs on kstream, after both halves of
-  // step t and beside step t+1. A step that writes the state buffer x[i] (or a bits
-  // buffer) an unfinished kNN reads waits for that kNN's event first; every other API
-  // call joins kstream into `stream` (use_dev).
-  // The fused step's rim kNN (mode 2) is not on kstream: after a split step it goes out
-  // as two launches on the step streams themselves, envs [0, B0) behind `stream`'s half
-  // and [B0, B) behind stream2's, so each half of the next step follows its own rim by
-  // stream order and the halves keep drifting out of phase (Flocking-v0).
-  hipStream_t kstream = nullptr;
-  hipEvent_t ev_kin[2] = {nullptr, nullptr};  // stream / stream2 -> kstream
-  hipEvent_t ev_kjoin = nullptr;              // kstream -> stream
-  bool k_pending = false;                     // kstream holds work `stream` has not waited for
-  int last_b0 = 0;                            // B0 of the last launch if it was split, else 0
-  struct KnnReader {
-    hipEvent_t ev = nullptr;                  // the kNN launch on kstream
-    bool live = false;
-    unsigned bmask = 0;                       // bits buffers it reads
-  } kread[2];                                 // by the state buffer x[i] the kNN reads
-  // fe_reset_device / fe_set_rng: the envs' MT19937 streams and the reset's outputs,
-  // allocated on first use (ensure_rng)
-  uint32_t* rng_key = nullptr;                // (B,624)
-  int32_t* rng_pos = nullptr;                 // (B)
-  int32_t* reset_tries = nullptr;             // (B)
-  uint8_t* reset_status = nullptr;            // (B)
-  int32_t* reset_envs = nullptr;              // (B) the selected envs of a masked reset
-  int32_t* reset_envs_host = nullptr;         // (B) page-locked: the list's upload reads it
-  hipEvent_t ev_envs = nullptr;               // that upload (before the list is rewritten)
-  std::vector<uint8_t> rng_set;               // (B) the env's stream was seeded or set
-};
 
 namespace {
 
@@ -303,10 +104,12 @@ int wait_knn_readers(fe_handle* h, int xw, int bw) {
   return GF_OK;
 }
 
+}  // namespace
+
 // Every API call except the step launches: the device, and `stream` ordered after all
 // of the handle's outstanding work; what it enqueues is ordered before the next
 // second-half launch (main_dirty).
-int use_dev(fe_handle* h) {
+int gf::use_dev(fe_handle* h) {
   GF_HIP(hipSetDevice(h->cfg.device));
   if (int rc = join_s2(h)) return rc;
   if (int rc = join_k(h)) return rc;
@@ -317,144 +120,18 @@ int use_dev(fe_handle* h) {
 }
 
 // The step path: only the device (the halves order themselves, see launch_step_split).
-int use_dev_step(fe_handle* h) {
+int gf::use_dev_step(fe_handle* h) {
   GF_HIP(hipSetDevice(h->cfg.device));
   return GF_OK;
 }
 
-template <class T>
-int dalloc(T** p, size_t count) {
-  if (count == 0) {
-    *p = nullptr;
-    return GF_OK;
-  }
-  hipError_t e = gf::device_alloc(reinterpret_cast<void**>(p), count * sizeof(T));
-  if (e != hipSuccess) return fail(GF_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+int gf::d2h(fe_handle* h, void* dst, const void* src, size_t bytes) {
+  GF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
-// ---- the process's communicator worker
-// ncclCommAbort runs on one thread per process that lives until the process exits (never
-// on a short-lived thread: RCCL's own threads may keep using the HIP thread-local state of
-// the thread that called into it, and a thread that exited under them corrupted the heap
-// once torch's HIP runtime was bound). The worker and its queue are never
-// destroyed, so the thread outlives static destruction.
-struct CommWorker {
-  std::mutex mu;
-  std::condition_variable cv;
-  std::deque<std::pair<ncclComm_t, int>> q;  // (communicator, device)
-};
-
-CommWorker* comm_worker() {
-  static CommWorker* w = [] {
-    auto* p = new CommWorker();
-    std::thread([p] {
-      for (;;) {
-        std::pair<ncclComm_t, int> job;
-        {
-          std::unique_lock<std::mutex> l(p->mu);
-          p->cv.wait(l, [p] { return !p->q.empty(); });
-          job = p->q.front();
-          p->q.pop_front();
-        }
-        hipSetDevice(job.second);
-        ncclCommAbort(job.first);
-      }
-    }).detach();
-    return p;
-  }();
-  return w;
-}
-
-void abort_comm_later(ncclComm_t c, int device) {
-  CommWorker* w = comm_worker();
-  {
-    std::lock_guard<std::mutex> l(w->mu);
-    w->q.emplace_back(c, device);
-  }
-  w->cv.notify_one();
-}
-
-// A thread that called into RCCL's initialisation parks here for the rest of the process
-// instead of exiting (the same thread-local-state reason as the worker above).
-[[noreturn]] void park_thread() {
-  static std::mutex* m = new std::mutex();
-  static std::condition_variable* cv = new std::condition_variable();
-  std::unique_lock<std::mutex> l(*m);
-  for (;;) cv->wait(l);
-}
-
-using Clock = std::chrono::steady_clock;
-
-Clock::time_point deadline_in(double seconds) {
-  return Clock::now() + std::chrono::microseconds(static_cast<int64_t>(seconds * 1e6));
-}
-
-// Every collective on the side stream complete, polled against the collective timeout and
-// the communicator's async error; false when it expired (a peer stopped responding).
-bool comm_stream_drained(fe_handle* h) {
-  if (!h->comm_stream) return true;
-  const auto deadline = deadline_in(h->comm_timeout);
-  for (int spin = 0;; ++spin) {
-    const hipError_t q = hipStreamQuery(h->comm_stream);
-    if (q != hipErrorNotReady) return q == hipSuccess;
-    ncclResult_t st = ncclSuccess;
-    if (h->comm && (ncclCommGetAsyncError(h->comm, &st) != ncclSuccess || (st != ncclSuccess && st != ncclInProgress)))
-      return false;
-    if (Clock::now() > deadline) return false;
-    if (spin > 64) std::this_thread::sleep_for(std::chrono::microseconds(50));
-  }
-}
-
-// Tear down the metrics path: the communicator (aborted when a collective may never
-// complete, else destroyed once the side stream has drained) and everything fe_comm_init
-// made for it, so that a later fe_comm_init starts from scratch.
-//
-// abort: a collective (or the initialisation) may never finish because a peer is gone.
-// The communicator is then aborted on the process's communicator worker, and the side
-// stream, its events and the buffers its collectives use are abandoned rather than
-// synchronised or freed (a kernel of the aborted collective may still touch them), so
-// that this call cannot hang; the step streams never wait on the side stream. A
-// non-abort release whose side stream does not drain within the collective timeout
-// becomes an abort.
-void comm_release(fe_handle* h, bool abort) {
-  if (!abort && h->comm && !comm_stream_drained(h)) abort = true;
-  if (abort) {
-    if (h->comm) abort_comm_later(h->comm, h->cfg.device);
-    h->comm = nullptr;
-    h->comm_stream = nullptr;
-    h->step_ev = h->step_ev2 = nullptr;
-    h->ring_reads.clear();  // copies the side stream may still run: abandoned, and so
-    h->stage_done = h->stage_done_dev = nullptr;  // is the word they would store into
-    h->gsend = h->gather = h->ssend = h->stats_gather = nullptr;
-  }
-  if (h->comm) {
-    ncclCommDestroy(h->comm);
-    h->comm = nullptr;
-  }
-  if (h->comm_stream) {
-    hipStreamSynchronize(h->comm_stream);  // drained above
-    hipStreamDestroy(h->comm_stream);
-    h->comm_stream = nullptr;
-  }
-  for (hipEvent_t* e : {&h->step_ev, &h->step_ev2})
-    if (*e) {
-      hipEventDestroy(*e);
-      *e = nullptr;
-    }
-  h->ring_reads.clear();
-  for (double** p : {&h->gsend, &h->gather, &h->ssend, &h->stats_gather})
-    if (*p) {
-      hipFree(*p);
-      *p = nullptr;
-    }
-  h->ag_issued = h->sg_pending = false;
-  h->last_count = 0;
-  h->nranks = 1;
-  h->rank = 0;
-  h->max_envs = 0;
-  h->shard_sizes.clear();
-}
+namespace {
 
 void release(fe_handle* h) {
   if (!h) return;
@@ -476,7 +153,7 @@ void release(fe_handle* h) {
     if (p) hipFree(p);
   if (h->reset_envs_host) hipHostFree(h->reset_envs_host);
   if (h->ev_envs) hipEventDestroy(h->ev_envs);
-  if (h->stage_done) hipHostFree(h->stage_done);  // (the side stream drained or was never used)
+  if (h->met.stage_done) hipHostFree(h->met.stage_done);  // (the side stream drained or was never used)
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
   if (h->h2d_ev) hipEventDestroy(h->h2d_ev);
   for (hipEvent_t e : {h->ev_s2, h->ev_main, h->tw[0], h->tw[1], h->ev_kin[0], h->ev_kin[1], h->ev_kjoin,
@@ -499,48 +176,14 @@ int check_env(const fe_handle* h, int env) {
 
 double* cur_reward(fe_handle* h) { return h->reward_ring + (size_t)h->rslot * h->cfg.n_envs; }
 
-// completion words of the side stream (fe_handle::stage_done)
-enum { kWordRing = 0, kWordStatsCopy = 1, kWordRewardGather = 2, kWordStatsGather = 3 };
-int stage_wait(fe_handle* h, int word, uint32_t seq, const char* what);
-
-// Whether the side-stream work numbered `seq` on completion word `word` is done (each
-// word's kernels run in order on the side stream, so the word only grows).
-bool stage_complete(const fe_handle* h, int word, uint32_t seq) {
-  return static_cast<int32_t>(__atomic_load_n(h->stage_done + word, __ATOMIC_ACQUIRE) - seq) >= 0;
-}
-
-int no_comm(const fe_handle* h) {
-  return fail(GF_ESTATE, "no communicator (fe_comm_init not called, or it was torn down" +
-                             (h->comm_lost.empty() ? std::string(")") : ": " + h->comm_lost + ")"));
-}
-
 // Advance the reward ring before a launch that writes rewards. The slot last held the
-// step kRewardSlots launches back. A reward gather's staging copy (on the side stream,
-// behind the previous collectives) that may still read it has normally finished long
-// ago: its event is queried on the host. If not, the host waits for it, bounded by the
-// collective timeout; on expiry (a collective stuck on a peer that stopped responding)
-// the metrics path is torn down (the communicator aborted, the reason kept for the next
-// metrics call) and the step goes on. The step streams never wait on the side stream on
-// the device, so nothing queued behind a stuck collective can stall them.
+// step kRewardSlots launches back; a reward gather's staging copy may still read it
+// (ring_reads_wait: a bounded host wait, after which the step goes on either way).
 int next_reward_slot(fe_handle* h) {
   const int64_t s = h->steps_written;
   h->rslot = static_cast<int>(s % kRewardSlots);
-  while (!h->ring_reads.empty() && h->ring_reads.front().first <= s - kRewardSlots) {
-    const uint32_t seq = h->ring_reads.front().seq;
-    const bool done = stage_complete(h, kWordRing, seq);
-    h->dbg[0]++;
-    h->dbg[1] = done ? 1 : 0;
-    h->dbg[2] = -1;
-    if (!done) {
-      h->dbg[2] = stage_wait(h, kWordRing, seq, "reward all-gather staging copy (ring slot reuse)");
-      if (h->dbg[2] == GF_ECOMM) {
-        h->comm_lost = g_err;  // comm_release emptied ring_reads: the step goes on
-        break;
-      }
-      if (h->dbg[2] != GF_OK) return h->dbg[2];
-    }
-    h->ring_reads.pop_front();
-  }
+  if (!h->met.ring_reads.empty())
+    if (int rc = ring_reads_wait(h, s)) return rc;
   h->steps_written = s + 1;
   return GF_OK;
 }
@@ -831,9 +474,34 @@ hipError_t clear_knn_history(fe_handle* h) {
   return hipSuccess;
 }
 
-int d2h(fe_handle* h, void* dst, const void* src, size_t bytes) {
-  GF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-  GF_HIP(hipStreamSynchronize(h->stream));
+// The envs' stream buffers and the device reset's outputs, on first use (zeroed).
+int ensure_rng(fe_handle* h) {
+  if (h->rng_key) return GF_OK;
+  const size_t B = h->cfg.n_envs;
+  int rc;
+  if ((rc = dalloc(&h->rng_key, B * gf::kMtN)) || (rc = dalloc(&h->rng_pos, B)) || (rc = dalloc(&h->reset_tries, B)) ||
+      (rc = dalloc(&h->reset_status, B)) || (rc = dalloc(&h->reset_envs, B)))
+    return rc;
+  GF_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->reset_envs_host), B * sizeof(int32_t), hipHostMallocDefault));
+  GF_HIP(hipEventCreateWithFlags(&h->ev_envs, hipEventDisableTiming));
+  GF_HIP(hipMemsetAsync(h->rng_key, 0, B * gf::kMtN * sizeof(uint32_t), h->stream));
+  GF_HIP(hipMemsetAsync(h->rng_pos, 0, B * sizeof(int32_t), h->stream));
+  GF_HIP(hipMemsetAsync(h->reset_tries, 0, B * sizeof(int32_t), h->stream));
+  GF_HIP(hipMemsetAsync(h->reset_status, 0, B, h->stream));
+  h->rng_set.assign(B, 0);
+  return GF_OK;
+}
+
+// The host-action copy stream and its two device buffers (fe_handle::ustream), on first use.
+int ensure_ucopy(fe_handle* h) {
+  if (h->ustream) return GF_OK;
+  for (int k = 0; k < 2; ++k) {
+    if (int rc = dalloc(reinterpret_cast<double**>(&h->ubuf[k]), h->BN * 2)) return rc;
+    GF_HIP(hipEventCreateWithFlags(&h->ev_ucopy[k], hipEventDisableTiming));
+    GF_HIP(hipEventCreateWithFlags(&h->ev_uread[k][0], hipEventDisableTiming));
+    GF_HIP(hipEventCreateWithFlags(&h->ev_uread[k][1], hipEventDisableTiming));
+  }
+  GF_HIP(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
   return GF_OK;
 }
 
@@ -857,10 +525,7 @@ int fe_create(const fe_config* cfg, fe_handle** out) {
     if (!found) return fail(GF_EINVAL, "n_neighbors must be one of 1-8, 10, 12, 16");
   }
   if (!(cfg->comm_radius > 0) || !(cfg->action_scalar != 0)) return fail(GF_EINVAL, "bad comm_radius/action_scalar");
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev == 0) return fail(GF_EHIP, "no HIP device available (libgymflock needs an MI355X)");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(GF_EINVAL, "device ordinal out of range");
+  if (int rc = select_device(cfg->device)) return rc;
 
   fe_handle* h = new fe_handle();
   h->cfg = *cfg;
@@ -886,8 +551,8 @@ int fe_create(const fe_config* cfg, fe_handle** out) {
     return fail(GF_EINVAL, "grid too large");
   }
   int rc = GF_OK;
-  if ((e = hipSetDevice(cfg->device)) != hipSuccess ||
-      (e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) {
+  hipError_t e;
+  if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) {
     release(h);
     return fail_hip("stream create", e);
   }
@@ -1035,30 +700,6 @@ int fe_get_state_env(fe_handle* h, int env, double* x) {
   return d2h(h, x, h->x[h->cur] + env * n, n * sizeof(double));
 }
 
-}  // extern "C"
-
-namespace {
-// The envs' stream buffers and the device reset's outputs, on first use (zeroed).
-int ensure_rng(fe_handle* h) {
-  if (h->rng_key) return GF_OK;
-  const size_t B = h->cfg.n_envs;
-  int rc;
-  if ((rc = dalloc(&h->rng_key, B * gf::kMtN)) || (rc = dalloc(&h->rng_pos, B)) || (rc = dalloc(&h->reset_tries, B)) ||
-      (rc = dalloc(&h->reset_status, B)) || (rc = dalloc(&h->reset_envs, B)))
-    return rc;
-  GF_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->reset_envs_host), B * sizeof(int32_t), hipHostMallocDefault));
-  GF_HIP(hipEventCreateWithFlags(&h->ev_envs, hipEventDisableTiming));
-  GF_HIP(hipMemsetAsync(h->rng_key, 0, B * gf::kMtN * sizeof(uint32_t), h->stream));
-  GF_HIP(hipMemsetAsync(h->rng_pos, 0, B * sizeof(int32_t), h->stream));
-  GF_HIP(hipMemsetAsync(h->reset_tries, 0, B * sizeof(int32_t), h->stream));
-  GF_HIP(hipMemsetAsync(h->reset_status, 0, B, h->stream));
-  h->rng_set.assign(B, 0);
-  return GF_OK;
-}
-}  // namespace
-
-extern "C" {
-
 int fe_reset_device(fe_handle* h, const fe_reset_config* rc, uint64_t seed, const uint8_t* env_mask, int flags,
                     int32_t* tries, uint8_t* status) {
   if (!h || !rc) return fail(GF_EINVAL, "null argument");
@@ -1197,25 +838,6 @@ int fe_compute_helpers(fe_handle* h, int flags) {
     if (int rc = launch_knn_cur(h, km)) return rc;
   return GF_OK;
 }
-
-}  // extern "C"
-
-namespace {
-// The host-action copy stream and its two device buffers (fe_handle::ustream), on first use.
-int ensure_ucopy(fe_handle* h) {
-  if (h->ustream) return GF_OK;
-  for (int k = 0; k < 2; ++k) {
-    if (int rc = dalloc(reinterpret_cast<double**>(&h->ubuf[k]), h->BN * 2)) return rc;
-    GF_HIP(hipEventCreateWithFlags(&h->ev_ucopy[k], hipEventDisableTiming));
-    GF_HIP(hipEventCreateWithFlags(&h->ev_uread[k][0], hipEventDisableTiming));
-    GF_HIP(hipEventCreateWithFlags(&h->ev_uread[k][1], hipEventDisableTiming));
-  }
-  GF_HIP(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
-  return GF_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int fe_step(fe_handle* h, const void* u, int flags) {
   if (!h) return fail(GF_EINVAL, "null handle");
@@ -1546,7 +1168,6 @@ int fe_get_stats_ex(fe_handle* h, int env, double* vel_diffs, double* min_dists,
   return GF_OK;
 }
 
-namespace {
 // get_stats (:136-143) on every env of the current state, then each env's means of the
 // two arrays into stats_sum (B,2), on the handle's stream. A pending stats gather's
 // staging copy may still read stats_sum: the host waits for that gather (bounded, as
@@ -1559,11 +1180,8 @@ int stats_summary_dev(fe_handle* h) {
   }
   if (!h->stats_sum)
     if (int rc = dalloc(&h->stats_sum, (size_t)h->cfg.n_envs * 2)) return rc;
-  if (h->sg_pending && h->comm && !stage_complete(h, kWordStatsCopy, h->stage_seq[kWordStatsCopy])) {
-    const int rc = stage_wait(h, kWordStatsCopy, h->stage_seq[kWordStatsCopy], "stats all-gather (send block reuse)");
-    if (rc == GF_ECOMM) h->comm_lost = g_err;  // torn down: the summary goes on
-    else if (rc != GF_OK) return rc;
-  }
+  if (h->met.sg_pending)
+    if (int rc = stats_send_wait(h)) return rc;
   gf::StatsArgs s{h->x[h->cur], h->vel_diffs, h->min_dists, h->degree,
                   h->cfg.comm_radius * h->cfg.comm_radius, h->cfg.n_agents, h->cfg.n_envs};
   hipError_t e = gf::launch_stats(s, h->stream);
@@ -1571,7 +1189,6 @@ int stats_summary_dev(fe_handle* h) {
   if (e != hipSuccess) return fail_hip("stats launch", e);
   return GF_OK;
 }
-}  // namespace
 
 int fe_stats_summary(fe_handle* h, double* dst) {
   if (!h || !dst) return fail(GF_EINVAL, "null argument");
@@ -1747,7 +1364,7 @@ int fe_sync(fe_handle* h) {
   if (!h) return fail(GF_EINVAL, "null handle");
   if (int rc = use_dev(h)) return rc;
   GF_HIP(hipStreamSynchronize(h->stream));
-  if (h->comm && !comm_stream_drained(h)) {
+  if (h->met.comm && !comm_stream_drained(h)) {
     comm_release(h, true);
     return fail(GF_ECOMM, "fe_sync: a collective did not complete within the timeout (a rank stopped "
                           "responding); communicator aborted, the handle keeps stepping");
@@ -1848,519 +1465,4 @@ int fe_diag(fe_handle* h, int what, int reps, double* avg_ms) {
   return GF_OK;
 }
 
-// ------------------------------------------------------------------ RCCL metrics path
-int fe_comm_unique_id(uint8_t id[128]) {
-  if (!id) return fail(GF_EINVAL, "null argument");
-  ncclUniqueId uid;
-  ncclResult_t r = ncclGetUniqueId(&uid);
-  if (r != ncclSuccess) return fail(GF_ECOMM, std::string("ncclGetUniqueId: ") + ncclGetErrorString(r));
-  static_assert(sizeof(uid) == 128, "ncclUniqueId size");
-  std::memcpy(id, &uid, 128);
-  return GF_OK;
-}
-
-int fe_check_shard_sizes(int nranks, const int32_t* n_envs) {
-  if (nranks < 1 || !n_envs) return fail(GF_EINVAL, "bad argument");
-  for (int r = 0; r < nranks; ++r)
-    if (n_envs[r] < 1) {
-      std::string m = "bad env shard sizes over ranks (every rank holds at least one env): n_envs =";
-      for (int q = 0; q < nranks; ++q) m += " " + std::to_string(n_envs[q]);
-      return fail(GF_ECOMM, m);
-    }
-  return GF_OK;
-}
-
 }  // extern "C"
-
-namespace {
-// A non-blocking communicator's pending work: poll its async error until it leaves
-// ncclInProgress or the deadline passes; then the metrics path is torn down (the
-// communicator aborted), so no rank waits forever on a peer that never joined or died.
-int comm_wait(fe_handle* h, Clock::time_point deadline, const char* what) {
-  for (;;) {
-    ncclResult_t st = ncclSuccess;
-    ncclResult_t r = ncclCommGetAsyncError(h->comm, &st);
-    if (r != ncclSuccess) st = r;
-    if (st == ncclSuccess) return GF_OK;
-    if (st != ncclInProgress || Clock::now() > deadline) {
-      comm_release(h, true);
-      h->comm_lost = std::string(what) + ": " +
-                     (st != ncclInProgress ? std::string(ncclGetErrorString(st))
-                                           : std::string("timed out (a rank did not join or stopped responding)")) +
-                     "; communicator aborted";
-      return fail(GF_ECOMM, h->comm_lost);
-    }
-    std::this_thread::sleep_for(std::chrono::microseconds(200));
-  }
-}
-
-// Wait for side-stream work `seq` on completion word `word` (a gather's staging copy or
-// its collective), polling the communicator's async error beside it: on expiry of the
-// collective timeout (a rank that died mid-run never posts its part) or a communicator
-// error the metrics path is torn down (GF_ECOMM, comm_lost says why); a side stream that
-// finished without the word is a HIP error (the path stays up).
-int stage_wait(fe_handle* h, int word, uint32_t seq, const char* what) {
-  const auto deadline = deadline_in(h->comm_timeout);
-  for (int spin = 0;; ++spin) {
-    h->dbg[7] = spin;
-    if (stage_complete(h, word, seq)) return GF_OK;
-    if ((spin & 63) == 63) {
-      const hipError_t q = hipStreamQuery(h->comm_stream);
-      if (q == hipSuccess && !stage_complete(h, word, seq))
-        return fail(GF_EHIP, std::string(what) + ": the side stream finished without the copy's completion word");
-      if (q != hipSuccess && q != hipErrorNotReady) return fail_hip(what, q);
-    }
-    ncclResult_t st = ncclSuccess;
-    ncclResult_t r = ncclCommGetAsyncError(h->comm, &st);
-    if (r != ncclSuccess) st = r;
-    if (spin == 0) h->dbg[3] = static_cast<int32_t>(st);
-    const bool err = st != ncclSuccess && st != ncclInProgress;
-    if (err || Clock::now() > deadline) {
-      comm_release(h, true);
-      h->comm_lost = std::string(what) + ": " +
-                     (err ? std::string(ncclGetErrorString(st)) : std::string("timed out (a rank stopped responding)")) +
-                     "; communicator aborted";
-      return fail(GF_ECOMM, h->comm_lost);
-    }
-    if (spin > 64) std::this_thread::sleep_for(std::chrono::microseconds(50));
-  }
-}
-
-// A collective just enqueued on the non-blocking communicator: wait until it is queued.
-int comm_enqueued(fe_handle* h, ncclResult_t r, const char* what) {
-  if (r == ncclInProgress) return comm_wait(h, deadline_in(h->comm_timeout), what);
-  if (r != ncclSuccess) {
-    comm_release(h, true);
-    h->comm_lost = std::string(what) + ": " + ncclGetErrorString(r) + "; communicator aborted";
-    return fail(GF_ECOMM, h->comm_lost);
-  }
-  return GF_OK;
-}
-
-// A zeroed device buffer of the metrics path (the pad columns of the send blocks are
-// never written afterwards).
-template <class T>
-int comm_alloc(fe_handle* h, T** p, size_t count) {
-  if (int rc = dalloc(p, count)) return rc;
-  if (*p) GF_HIP(hipMemsetAsync(*p, 0, count * sizeof(T), h->comm_stream));
-  return GF_OK;
-}
-
-// fe_comm_init once the communicator exists: the side stream, the shard-size exchange
-// and the gather buffers. On failure the caller tears everything down.
-int comm_setup(fe_handle* h, int nranks, int rank, Clock::time_point deadline) {
-  GF_HIP(hipStreamCreateWithFlags(&h->comm_stream, hipStreamNonBlocking));
-  if (!h->stage_done) {
-    void* p = nullptr;
-    GF_HIP(hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    h->stage_done = static_cast<uint32_t*>(p);
-    for (int w = 0; w < 4; ++w)  // every earlier sequence number: done
-      __atomic_store_n(h->stage_done + w, h->stage_seq[w], __ATOMIC_SEQ_CST);
-    void* d = nullptr;
-    GF_HIP(hipHostGetDevicePointer(&d, p, 0));
-    h->stage_done_dev = static_cast<uint32_t*>(d);
-  }
-  // every rank's shard size, before any gather pads to the largest
-  int32_t* dsz = nullptr;
-  if (int rc = dalloc(&dsz, (size_t)nranks)) return rc;
-  std::vector<int32_t> sizes(nranks);
-  const int32_t mine = h->cfg.n_envs;
-  int rc = GF_OK;
-  const hipError_t e = hipMemcpyAsync(dsz + rank, &mine, 4, hipMemcpyHostToDevice, h->comm_stream);
-  if (e != hipSuccess) rc = fail_hip("shard-size upload", e);
-  if (rc == GF_OK) {
-    const ncclResult_t r = ncclAllGather(dsz + rank, dsz, 1, ncclInt32, h->comm, h->comm_stream);
-    rc = (r == ncclSuccess || r == ncclInProgress) ? comm_wait(h, deadline, "shard-size all-gather")
-                                                   : fail(GF_ECOMM, std::string("ncclAllGather: ") + ncclGetErrorString(r));
-  }
-  if (rc == GF_OK) {
-    hipError_t q;
-    while ((q = hipStreamQuery(h->comm_stream)) == hipErrorNotReady) {
-      if (Clock::now() > deadline) break;
-      std::this_thread::sleep_for(std::chrono::microseconds(200));
-    }
-    if (q == hipErrorNotReady) {
-      rc = fail(GF_ECOMM, "shard-size all-gather: timed out (a rank stopped responding)");
-    } else if (q != hipSuccess) {
-      rc = fail(GF_EHIP, std::string("shard-size all-gather: ") + hipGetErrorString(q));
-    } else if (hipMemcpyAsync(sizes.data(), dsz, 4 * (size_t)nranks, hipMemcpyDeviceToHost, h->comm_stream) !=
-                   hipSuccess ||
-               hipStreamSynchronize(h->comm_stream) != hipSuccess) {
-      rc = fail(GF_EHIP, "shard-size copy");
-    } else {
-      rc = fe_check_shard_sizes(nranks, sizes.data());
-    }
-  }
-  hipFree(dsz);
-  if (rc != GF_OK) return rc;
-  h->shard_sizes = sizes;
-  h->max_envs = *std::max_element(sizes.begin(), sizes.end());
-  const size_t W = h->max_envs;
-  for (hipEvent_t* e : {&h->step_ev, &h->step_ev2})
-    GF_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  if ((rc = comm_alloc(h, &h->gsend, (size_t)kRewardSlots * W)) ||
-      (rc = comm_alloc(h, &h->gather, (size_t)nranks * kRewardSlots * W)) || (rc = comm_alloc(h, &h->ssend, W * 2)) ||
-      (rc = comm_alloc(h, &h->stats_gather, (size_t)nranks * W * 2)))
-    return rc;
-  GF_HIP(hipStreamSynchronize(h->comm_stream));
-  h->nranks = nranks;
-  h->rank = rank;
-  h->gathered_upto = h->steps_written;  // the first gather ships the steps after init
-  return GF_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int fe_comm_init_timeout(fe_handle* h, int nranks, int rank, const uint8_t id[128], double timeout_s) {
-  if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks || !(timeout_s > 0)) return fail(GF_EINVAL, "bad argument");
-  if (h->comm) return fail(GF_ESTATE, "communicator already initialised");
-  if (int rc = use_dev(h)) return rc;
-  const auto deadline = deadline_in(timeout_s);
-  h->comm_timeout = timeout_s;
-  ncclUniqueId uid;
-  std::memcpy(&uid, id, 128);
-  // RCCL's non-blocking init still connects to the bootstrap root inside the call, which
-  // waits for every rank: with a rank missing it never returns. The call therefore runs
-  // on a thread of its own, which also waits for the communicator to leave
-  // ncclInProgress (RCCL's own init thread works on the creating thread's HIP state:
-  // with torch's HIP runtime bound, a creating thread that exited first left a corrupted
-  // heap) and then parks for the rest of the process instead of exiting. It hands the
-  // communicator over through `state`: 0 running, 1 handed over, 2 abandoned by this call
-  // at the deadline (the helper then queues what it created for the communicator
-  // worker's abort), so exactly one side owns the communicator. This rank then fails
-  // with GF_ECOMM, its handle still usable.
-  struct InitJob {
-    ncclComm_t comm = nullptr;
-    ncclResult_t r = ncclInProgress;
-    std::atomic<int> state{0};
-  };
-  auto job = std::make_shared<InitJob>();
-  const int dev = h->cfg.device;
-  std::thread([job, nranks, uid, rank, dev]() {
-    hipSetDevice(dev);
-    ncclConfig_t config = NCCL_CONFIG_INITIALIZER;
-    config.blocking = 0;
-    ncclComm_t c = nullptr;
-    ncclResult_t rr = ncclCommInitRankConfig(&c, nranks, uid, rank, &config);
-    if (c && (rr == ncclSuccess || rr == ncclInProgress)) {
-      for (;;) {
-        ncclResult_t st = ncclSuccess;
-        const ncclResult_t q = ncclCommGetAsyncError(c, &st);
-        rr = q != ncclSuccess ? q : st;
-        if (rr != ncclInProgress || job->state.load(std::memory_order_acquire) == 2) break;
-        std::this_thread::sleep_for(std::chrono::microseconds(200));
-      }
-    }
-    job->comm = c;
-    job->r = rr;
-    int running = 0;
-    if (!job->state.compare_exchange_strong(running, 1, std::memory_order_acq_rel) && c)
-      abort_comm_later(c, dev);  // abandoned: nobody else will release it
-    park_thread();
-  }).detach();
-  while (job->state.load(std::memory_order_acquire) != 1) {
-    if (Clock::now() > deadline) {
-      int running = 0;
-      if (job->state.compare_exchange_strong(running, 2, std::memory_order_acq_rel))
-        return fail(GF_ECOMM, "ncclCommInitRankConfig: timed out (a rank did not join); the initialisation is aborted behind");
-      break;  // handed over just now
-    }
-    std::this_thread::sleep_for(std::chrono::microseconds(200));
-  }
-  h->comm = job->comm;
-  h->comm_lost.clear();
-  const ncclResult_t r = job->r;
-  if (r != ncclSuccess && r != ncclInProgress) {
-    comm_release(h, true);
-    return fail(GF_ECOMM, std::string("ncclCommInitRankConfig: ") + ncclGetErrorString(r));
-  }
-  if (int rc = comm_wait(h, deadline, "ncclCommInitRankConfig")) return rc;
-  if (int rc = comm_setup(h, nranks, rank, deadline)) {
-    const std::string msg = g_err;
-    comm_release(h, true);  // abort: a peer may still be inside the shard-size collective
-    return fail(rc, msg);
-  }
-  return GF_OK;
-}
-
-int fe_comm_init(fe_handle* h, int nranks, int rank, const uint8_t id[128]) {
-  return fe_comm_init_timeout(h, nranks, rank, id, kCommInitTimeoutS);
-}
-
-int fe_comm_info(fe_handle* h, int32_t* count, int32_t* user_rank, int32_t* device, char* bus_id, int bus_id_len) {
-  if (!h) return fail(GF_EINVAL, "null handle");
-  if (!h->comm) return no_comm(h);
-  int c = 0, ur = 0, d = 0;
-  ncclResult_t r = ncclCommCount(h->comm, &c);
-  if (r == ncclSuccess) r = ncclCommUserRank(h->comm, &ur);
-  if (r == ncclSuccess) r = ncclCommCuDevice(h->comm, &d);
-  if (r != ncclSuccess) return fail(GF_ECOMM, std::string("ncclComm query: ") + ncclGetErrorString(r));
-  if (count) *count = c;
-  if (user_rank) *user_rank = ur;
-  if (device) *device = d;
-  if (bus_id && bus_id_len > 0) GF_HIP(hipDeviceGetPCIBusId(bus_id, bus_id_len, d));
-  return GF_OK;
-}
-
-int fe_comm_shard_sizes(fe_handle* h, int32_t* sizes, int32_t* max_envs) {
-  if (!h) return fail(GF_EINVAL, "null handle");
-  if (!h->comm) return no_comm(h);
-  if (sizes) std::copy(h->shard_sizes.begin(), h->shard_sizes.end(), sizes);
-  if (max_envs) *max_envs = h->max_envs;
-  return GF_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// A reward gather's staging copy on the side stream: steps [s0, s0 + count) of the ring
-// (wrapping) into the padded send block, then `seq` into the page-locked completion word
-// with a system-scope release once every read of the ring has returned.
-__global__ __launch_bounds__(256) void ring_stage_kernel(const double* ring, int B, int s0, int count, double* gs,
-                                                         int W, uint32_t* done, uint32_t seq) {
-  const int n = count * B;
-  for (int k = threadIdx.x; k < n; k += 256) {
-    const int t = k / B, e = k - t * B;
-    gs[(size_t)t * W + e] = ring[(size_t)((s0 + t) % kRewardSlots) * B + e];
-  }
-  __syncthreads();  // every thread's loads returned (its stores used them)
-  if (threadIdx.x == 0) {
-    __threadfence_system();
-    __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
-// After a collective on the side stream: `seq` into its completion word (the stream's
-// earlier work, the collective included, is complete when this runs).
-__global__ __launch_bounds__(64) void signal_kernel(uint32_t* done, uint32_t seq) {
-  if (threadIdx.x == 0) {
-    __threadfence_system();
-    __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
-// The stats gather's send block: n doubles from the summaries, then `seq` into the
-// completion word once every read of them has returned.
-__global__ __launch_bounds__(256) void copy_signal_kernel(const double* src, double* dst, int n, uint32_t* done,
-                                                          uint32_t seq) {
-  for (int k = threadIdx.x; k < n; k += 256) dst[k] = src[k];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence_system();
-    __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-}  // namespace
-
-extern "C" {
-
-int fe_allgather_rewards(fe_handle* h) {
-  if (!h) return fail(GF_EINVAL, "null handle");
-  if (!h->comm) return no_comm(h);
-  // a step-path call: the gather's stream waits for both step streams' latest work
-  // (events only), so back-to-back split steps around it stay split and out of phase
-  // (use_dev's join would make the next step a single launch)
-  if (int rc = use_dev_step(h)) return rc;
-  const int64_t first = h->gathered_upto, count = h->steps_written - first;
-  if (count <= 0) return fail(GF_ESTATE, "no step since the last reward all-gather");
-  if (count > kRewardSlots) {
-    // the ranks step in lockstep, so every rank takes this branch at the same call and
-    // none is left inside a collective
-    h->gathered_upto = h->steps_written;
-    return fail(GF_ESTATE, "the rewards of " + std::to_string(count - kRewardSlots) +
-                               " step(s) were overwritten before a gather (gather at least every " +
-                               std::to_string(kRewardSlots) + " steps)");
-  }
-  const size_t B = h->cfg.n_envs, W = h->max_envs;
-  // the side stream waits for both step streams' latest work (events only; the step
-  // streams never wait for the side stream)
-  GF_HIP(hipEventRecord(h->step_ev, h->stream));
-  GF_HIP(hipStreamWaitEvent(h->comm_stream, h->step_ev, 0));
-  if (h->stream2) {
-    GF_HIP(hipEventRecord(h->step_ev2, h->stream2));
-    GF_HIP(hipStreamWaitEvent(h->comm_stream, h->step_ev2, 0));
-  }
-  // the steps' ring slots (two runs when they wrap) into the padded send block, behind
-  // the previous collective (which read it) on the same stream
-  // and their completion into the page-locked word the ring-slot reuse polls: the copy
-  // kernel's own store, not an event query ("a step that did not wait")
-  double* gs = h->gsend;
-  const int s0 = static_cast<int>(first % kRewardSlots);
-  const uint32_t seq = ++h->stage_seq[kWordRing];
-  hipLaunchKernelGGL(ring_stage_kernel, dim3(1), dim3(256), 0, h->comm_stream, static_cast<const double*>(h->reward_ring),
-                     static_cast<int>(B), s0, static_cast<int>(count), gs, static_cast<int>(W),
-                     h->stage_done_dev + kWordRing, seq);
-  GF_HIP(hipGetLastError());
-  h->ring_reads.push_back({first, seq});
-  h->dbg[4] = static_cast<int32_t>(h->ring_reads.size());
-  h->dbg[5] = stage_complete(h, kWordRing, seq) ? 1 : 0;
-  if (int rc = comm_enqueued(h, ncclAllGather(gs, h->gather, (size_t)count * W, ncclFloat64, h->comm, h->comm_stream),
-                             "ncclAllGather (rewards)"))
-    return rc;
-  hipLaunchKernelGGL(signal_kernel, dim3(1), dim3(64), 0, h->comm_stream, h->stage_done_dev + kWordRewardGather,
-                     ++h->stage_seq[kWordRewardGather]);
-  GF_HIP(hipGetLastError());
-  h->ag_issued = true;
-  h->last_count = static_cast<int>(count);
-  h->gathered_upto = h->steps_written;
-  return GF_OK;
-}
-
-int fe_get_gathered_rewards(fe_handle* h, double* dst) {
-  if (!h || !dst) return fail(GF_EINVAL, "null argument");
-  if (!h->comm) return no_comm(h);
-  if (!h->ag_issued) return fail(GF_ESTATE, "no all-gather issued");
-  if (int rc = use_dev(h)) return rc;
-  if (int rc = stage_wait(h, kWordRewardGather, h->stage_seq[kWordRewardGather], "reward all-gather")) return rc;
-  const size_t n = (size_t)h->nranks * h->last_count * h->max_envs;
-  return d2h(h, dst, h->gather, n * 8);  // (on the handle's stream: no use of the null stream)
-}
-
-int fe_gathered_steps(fe_handle* h) { return h ? h->last_count : 0; }
-
-int fe_allgather_stats(fe_handle* h) {
-  if (!h) return fail(GF_EINVAL, "null handle");
-  if (!h->comm) return no_comm(h);
-  if (!h->has_state) return fail(GF_ESTATE, "state not set");
-  // the summaries are taken on the whole current state (both step halves joined); the
-  // collective then runs on the side stream, like the reward all-gather
-  if (int rc = use_dev(h)) return rc;
-  if (int rc = stats_summary_dev(h)) return rc;  // (after the previous stats gather, bounded)
-  if (!h->comm) return fail(GF_ECOMM, "metrics path torn down: " + h->comm_lost);
-  GF_HIP(hipEventRecord(h->step_ev, h->stream));
-  GF_HIP(hipStreamWaitEvent(h->comm_stream, h->step_ev, 0));
-  // into the padded send block, on the side stream (after the previous stats gather)
-  hipLaunchKernelGGL(copy_signal_kernel, dim3(1), dim3(256), 0, h->comm_stream, static_cast<const double*>(h->stats_sum),
-                     h->ssend, h->cfg.n_envs * 2, h->stage_done_dev + kWordStatsCopy, ++h->stage_seq[kWordStatsCopy]);
-  GF_HIP(hipGetLastError());
-  if (int rc = comm_enqueued(h, ncclAllGather(h->ssend, h->stats_gather, (size_t)h->max_envs * 2, ncclFloat64,
-                                              h->comm, h->comm_stream),
-                             "ncclAllGather (stats)"))
-    return rc;
-  hipLaunchKernelGGL(signal_kernel, dim3(1), dim3(64), 0, h->comm_stream, h->stage_done_dev + kWordStatsGather,
-                     ++h->stage_seq[kWordStatsGather]);
-  GF_HIP(hipGetLastError());
-  h->sg_pending = true;
-  return GF_OK;
-}
-
-int fe_get_gathered_stats(fe_handle* h, double* dst) {
-  if (!h || !dst) return fail(GF_EINVAL, "null argument");
-  if (!h->comm) return no_comm(h);
-  if (!h->sg_pending) return fail(GF_ESTATE, "no stats all-gather issued");
-  if (int rc = use_dev(h)) return rc;
-  if (int rc = stage_wait(h, kWordStatsGather, h->stage_seq[kWordStatsGather], "stats all-gather")) return rc;
-  return d2h(h, dst, h->stats_gather, (size_t)h->nranks * h->max_envs * 2 * sizeof(double));
-}
-
-int fe_comm_destroy(fe_handle* h) {
-  if (!h) return fail(GF_EINVAL, "null handle");
-  if (int rc = use_dev(h)) return rc;
-  comm_release(h, false);
-  return GF_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// fe_debug_comm_gate's kernel: one wave that sleeps until the page-locked flag turns
-// non-zero or `ticks` of the device's wall clock pass (always bounded).
-// flag[1] = 1 once it runs, flag[2] = 1 (opened) or 2 (timed out) as it ends.
-__global__ __launch_bounds__(64) void comm_gate_kernel(unsigned* flag, unsigned long long ticks) {
-  const unsigned long long t0 = wall_clock64();
-  if (threadIdx.x == 0) __hip_atomic_store(flag + 1, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  unsigned why = 1u;
-  while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == 0u) {
-    if (wall_clock64() - t0 > ticks) {
-      why = 2u;
-      break;
-    }
-    __builtin_amdgcn_s_sleep(127);
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(flag + 2, why, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// one process-wide gate flag (fine-grained page-locked memory), never freed: a gate
-// kernel abandoned with an aborted side stream may still read it
-unsigned* gate_flag() {
-  static unsigned* f = [] {
-    void* p = nullptr;
-    if (hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return (unsigned*)nullptr;
-    *static_cast<unsigned*>(p) = 1u;
-    return static_cast<unsigned*>(p);
-  }();
-  return f;
-}
-
-// the path of the shared object that defines the function at `fn`
-void so_path(const void* fn, char* dst, int len) {
-  if (!dst || len <= 0) return;
-  Dl_info info{};
-  const char* p = (dladdr(fn, &info) && info.dli_fname) ? info.dli_fname : "";
-  std::snprintf(dst, (size_t)len, "%s", p);
-}
-}  // namespace
-
-extern "C" {
-
-int fe_debug_comm_gate(fe_handle* h, int close, double max_seconds) {
-  if (!h) return fail(GF_EINVAL, "null handle");
-  unsigned* f = gate_flag();
-  if (!f) return fail(GF_ENOMEM, "gate flag: hipHostMalloc failed");
-  if (!close) {  // also after the communicator was aborted (its side stream abandoned)
-    __atomic_store_n(f, 1u, __ATOMIC_SEQ_CST);
-    return GF_OK;
-  }
-  if (!h->comm || !h->comm_stream) return fail(GF_ESTATE, "no communicator (fe_comm_init first)");
-  if (!(max_seconds > 0) || max_seconds > 120) return fail(GF_EINVAL, "max_seconds must be in (0, 120]");
-  GF_HIP(hipSetDevice(h->cfg.device));
-  int khz = 0;
-  GF_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->cfg.device));
-  void* df = nullptr;
-  GF_HIP(hipHostGetDevicePointer(&df, f, 0));
-  __atomic_store_n(f + 1, 0u, __ATOMIC_SEQ_CST);
-  __atomic_store_n(f + 2, 0u, __ATOMIC_SEQ_CST);
-  __atomic_store_n(f, 0u, __ATOMIC_SEQ_CST);
-  const unsigned long long ticks = static_cast<unsigned long long>(max_seconds * 1000.0 * (khz > 0 ? khz : 100000));
-  hipLaunchKernelGGL(comm_gate_kernel, dim3(1), dim3(64), 0, h->comm_stream, static_cast<unsigned*>(df), ticks);
-  GF_HIP(hipGetLastError());
-  h->dbg[6] = static_cast<int32_t>(hipStreamQuery(h->comm_stream));
-  return GF_OK;
-}
-
-int fe_debug_comm_state(fe_handle* h, int32_t* out) {
-  if (!h || !out) return fail(GF_EINVAL, "null argument");
-  for (int k = 0; k < 8; ++k) out[k] = h->dbg[k];
-  unsigned* f = gate_flag();
-  out[8] = f ? static_cast<int32_t>(__atomic_load_n(f + 1, __ATOMIC_SEQ_CST)) : -1;
-  out[9] = f ? static_cast<int32_t>(__atomic_load_n(f + 2, __ATOMIC_SEQ_CST)) : -1;
-  out[10] = h->comm ? 1 : 0;
-  out[11] = static_cast<int32_t>(h->ring_reads.size());
-  return GF_OK;
-}
-
-int fe_runtime_info(int32_t* hip_runtime_version, int32_t* hip_driver_version, int32_t* rccl_version, char* hip_path,
-                    int hip_path_len, char* rccl_path, int rccl_path_len) {
-  int v = 0;
-  if (hip_runtime_version) *hip_runtime_version = hipRuntimeGetVersion(&v) == hipSuccess ? v : 0;
-  v = 0;
-  if (hip_driver_version) {
-    *hip_driver_version = hipDriverGetVersion(&v) == hipSuccess ? v : 0;
-    (void)hipGetLastError();
-  }
-  v = 0;
-  if (rccl_version) *rccl_version = ncclGetVersion(&v) == ncclSuccess ? v : 0;
-  so_path(reinterpret_cast<const void*>(&hipRuntimeGetVersion), hip_path, hip_path_len);
-  so_path(reinterpret_cast<const void*>(&ncclGetVersion), rccl_path, rccl_path_len);
-  return GF_OK;
-}
-
-}  // extern "C"
-
-// flock_reset.hip is a source of its own in this directory's Makefile (GF_RESET_OWN_TU). A
-// build that lists the library's sources without it (the host-sanitizer build of the
-// C-ABI, tests/asan) gets its kernel and launcher here, with this file's flags.
-#ifndef GF_RESET_OWN_TU
-#include "flock_reset.hip"
-#endif

@@ -5,40 +5,11 @@
 #include <string>
 #include <vector>
 
+#include "capi_common.h"
 #include "coverage_internal.h"
-#include "device_alloc.h"
-#include "gymflock.h"
 
-namespace gf {
-int set_error(int code, const std::string& msg);
-}
-
-namespace {
-
-int cfail(int code, const std::string& m) { return gf::set_error(code, m); }
-
-#define CV_HIP(expr)                                                                 \
-  do {                                                                               \
-    hipError_t e_ = (expr);                                                          \
-    if (e_ != hipSuccess) return cfail(GF_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-template <class T>
-int calloc_dev(T** p, size_t n) {
-  *p = nullptr;
-  if (n == 0) return GF_OK;
-  hipError_t e = gf::device_alloc(reinterpret_cast<void**>(p), n * sizeof(T));
-  if (e != hipSuccess) return cfail(GF_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  e = hipMemset(*p, 0, n * sizeof(T));
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("hipMemset: ") + hipGetErrorString(e));
-  // hipMemset may still be running on the null stream, which the handle's non-blocking
-  // stream does not order against: finish it before any kernel writes the buffer
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("hipDeviceSynchronize: ") + hipGetErrorString(e));
-  return GF_OK;
-}
-
-}  // namespace
+using gf::dalloc_zero;
+using gf::fail;
 
 struct cov_handle {
   cov_config cfg{};
@@ -150,8 +121,8 @@ namespace {
 
 int join_s2(cov_handle* h) {
   if (h->s2_pending) {
-    CV_HIP(hipEventRecord(h->ev_s2, h->stream2));
-    CV_HIP(hipStreamWaitEvent(h->stream, h->ev_s2, 0));
+    GF_HIP(hipEventRecord(h->ev_s2, h->stream2));
+    GF_HIP(hipStreamWaitEvent(h->stream, h->ev_s2, 0));
     h->s2_pending = false;
   }
   return GF_OK;
@@ -160,7 +131,7 @@ int join_s2(cov_handle* h) {
 // Every call but cov_step: the device, `stream` after all outstanding work, and what
 // it enqueues ordered before the next second-half step.
 int use(cov_handle* h) {
-  CV_HIP(hipSetDevice(h->cfg.device));
+  GF_HIP(hipSetDevice(h->cfg.device));
   if (int rc = join_s2(h)) return rc;
   h->main_dirty = true;
   h->other_work = true;
@@ -197,22 +168,22 @@ void cov_release(cov_handle* h) {
 // Read and clear the device error bits; translate to a status.
 int check_err(cov_handle* h) {
   int err = 0;
-  CV_HIP(hipMemcpyAsync(&err, h->err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipMemcpyAsync(&err, h->err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   if (!err) return GF_OK;
-  CV_HIP(hipMemsetAsync(h->err, 0, sizeof(int), h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipMemsetAsync(h->err, 0, sizeof(int), h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   std::string m;
   if (err & 1) m += "a target has more than 4 motion-graph neighbours (coverage.py:257 assert); ";
   if (err & 2) m += "motion edges + 8*n_robots exceed 4*max_nodes (\"Increase MAX_EDGES\", coverage.py:288); ";
   if (err & 4) m += "action outside [0, 4) (coverage.py:189 index); ";
   if (err & 8) m += "greedy next hop is not among the robot's action targets (IndexError at coverage.py:869); ";
-  return cfail(GF_EINVAL, m);
+  return fail(GF_EINVAL, m);
 }
 
 int copy_out(cov_handle* h, void* dst, const void* src, size_t bytes) {
   if (!dst) return GF_OK;
-  CV_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
   return GF_OK;
 }
 
@@ -224,17 +195,17 @@ int ensure_time_matrix(cov_handle* h) {
   const int sched_stride = 4 * Tm * 16 + 16;  // motion edges <= 4 per target, batches <= 16, + prefetch slack
   if (!h->tm_cost) {
     int rc;
-    if ((rc = calloc_dev(&h->tm_cost, (size_t)B * Tm * Tm)) || (rc = calloc_dev(&h->tm_prevT, (size_t)B * Tm * Tm)) ||
-        (rc = calloc_dev(&h->tm_flags, (size_t)B * nchunk * kcap)) ||
-        (rc = calloc_dev(&h->needs_random, (size_t)B * h->cfg.n_robots)) || (rc = calloc_dev(&h->tm_envsel, (size_t)B)) ||
-        (rc = calloc_dev(&h->tm_sched, (size_t)B * sched_stride)) || (rc = calloc_dev(&h->tm_nslots, (size_t)B)) ||
-        (rc = calloc_dev(&h->tm_lev, (size_t)B * (4 * Tm + 2))) ||
-        (rc = calloc_dev(&h->tm_nlev, (size_t)B)) || (rc = calloc_dev(&h->tm_overflow, (size_t)B)) ||
-        (rc = calloc_dev(&h->tm_cost8, (size_t)B * Tm * Tm)) || (rc = calloc_dev(&h->tm_wide, (size_t)B)))
+    if ((rc = dalloc_zero(&h->tm_cost, (size_t)B * Tm * Tm)) || (rc = dalloc_zero(&h->tm_prevT, (size_t)B * Tm * Tm)) ||
+        (rc = dalloc_zero(&h->tm_flags, (size_t)B * nchunk * kcap)) ||
+        (rc = dalloc_zero(&h->needs_random, (size_t)B * h->cfg.n_robots)) || (rc = dalloc_zero(&h->tm_envsel, (size_t)B)) ||
+        (rc = dalloc_zero(&h->tm_sched, (size_t)B * sched_stride)) || (rc = dalloc_zero(&h->tm_nslots, (size_t)B)) ||
+        (rc = dalloc_zero(&h->tm_lev, (size_t)B * (4 * Tm + 2))) ||
+        (rc = dalloc_zero(&h->tm_nlev, (size_t)B)) || (rc = dalloc_zero(&h->tm_overflow, (size_t)B)) ||
+        (rc = dalloc_zero(&h->tm_cost8, (size_t)B * Tm * Tm)) || (rc = dalloc_zero(&h->tm_wide, (size_t)B)))
       return rc;
     if (Tm <= gf::kGreedyListMaxT) {  // rows padded to 16 bytes (greedy_from_list's loads)
       h->gstride = (Tm + gf::kGreedyListPad - 1) & ~(gf::kGreedyListPad - 1);
-      if ((rc = calloc_dev(&h->tm_glist, (size_t)B * Tm * h->gstride)) || (rc = calloc_dev(&h->tm_glen, (size_t)B * Tm)))
+      if ((rc = dalloc_zero(&h->tm_glist, (size_t)B * Tm * h->gstride)) || (rc = dalloc_zero(&h->tm_glen, (size_t)B * Tm)))
         return rc;
     }
     h->tm_wide_host.assign(B, 0);
@@ -253,7 +224,7 @@ int ensure_time_matrix(cov_handle* h) {
   }
   if (gf::cov_time_matrix_lds_bytes(t_lds, false) > 160 * 1024 ||
       gf::cov_tm_schedule_lds_bytes(t_lds, e_max) > 160 * 1024)
-    return cfail(GF_EINVAL, "time matrix: (n_targets + 1) * 64 bytes exceed the 160 KB LDS of a CU");
+    return fail(GF_EINVAL, "time matrix: (n_targets + 1) * 64 bytes exceed the 160 KB LDS of a CU");
   gf::CovTmArgs t{};
   t.R = h->a.R;
   t.M = h->a.M;
@@ -278,15 +249,15 @@ int ensure_time_matrix(cov_handle* h) {
   t.sched_stride = sched_stride;
   t.lev_off = h->tm_lev;
   t.lev_stride = 4 * Tm + 2;  // levels <= motion edges <= 4 per target, + the end offset
-  CV_HIP(hipMemcpyAsync(h->tm_envsel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->tm_envsel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   hipError_t e = gf::launch_cov_tm_schedule(t, (int)sel.size(), e_max, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_tm_schedule_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_tm_schedule_kernel: ") + hipGetErrorString(e));
   // uint8 entries first (twice the waves per CU); envs it cannot bound get uint16
   e = gf::launch_cov_time_matrix(t, (int)sel.size(), false, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_time_matrix_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_time_matrix_kernel: ") + hipGetErrorString(e));
   std::vector<uint8_t> ovf(B);
-  CV_HIP(hipMemcpyAsync(ovf.data(), h->tm_overflow, B, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipMemcpyAsync(ovf.data(), h->tm_overflow, B, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   std::vector<int32_t> wide;
   int t_wide = 0;
   for (int b : sel)
@@ -296,18 +267,18 @@ int ensure_time_matrix(cov_handle* h) {
     }
   if (!wide.empty()) {
     if (gf::cov_time_matrix_lds_bytes(t_wide, true) > 160 * 1024)
-      return cfail(GF_EINVAL, "time matrix: hop counts above 254 need (n_targets + 1) * 128 bytes of LDS (> 160 KB)");
-    CV_HIP(hipMemsetAsync(h->tm_overflow, 0, B, h->stream));
-    CV_HIP(hipMemcpyAsync(h->tm_envsel, wide.data(), wide.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+      return fail(GF_EINVAL, "time matrix: hop counts above 254 need (n_targets + 1) * 128 bytes of LDS (> 160 KB)");
+    GF_HIP(hipMemsetAsync(h->tm_overflow, 0, B, h->stream));
+    GF_HIP(hipMemcpyAsync(h->tm_envsel, wide.data(), wide.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     t.t_lds = t_wide;
     e = gf::launch_cov_time_matrix(t, (int)wide.size(), true, h->stream);
-    if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_time_matrix_kernel: ") + hipGetErrorString(e));
-    CV_HIP(hipStreamSynchronize(h->stream));
+    if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_time_matrix_kernel: ") + hipGetErrorString(e));
+    GF_HIP(hipStreamSynchronize(h->stream));
   }
   h->tm_wide_envs += (int64_t)wide.size();
   for (int b : sel) h->tm_wide_host[b] = 0;
   for (int b : wide) h->tm_wide_host[b] = 1;
-  CV_HIP(hipMemcpyAsync(h->tm_wide, h->tm_wide_host.data(), B, hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->tm_wide, h->tm_wide_host.data(), B, hipMemcpyHostToDevice, h->stream));
   if (h->tm_glist) {  // every selected env's greedy lists, from its final matrix
     t.wide = h->tm_wide;
     t.nbr = h->a.nbr;
@@ -315,11 +286,11 @@ int ensure_time_matrix(cov_handle* h) {
     t.glist = h->tm_glist;
     t.glen = h->tm_glen;
     t.gstride = h->gstride;
-    CV_HIP(hipMemcpyAsync(h->tm_envsel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    GF_HIP(hipMemcpyAsync(h->tm_envsel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     e = gf::launch_cov_greedy_lists(t, (int)sel.size(), h->stream);
-    if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_greedy_list_kernel: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_greedy_list_kernel: ") + hipGetErrorString(e));
   }
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   for (int b : sel) h->tm_valid[b] = 1;
   h->tm_ready = true;
   return GF_OK;
@@ -361,7 +332,7 @@ gf::CovHiddenArgs hidden_args(const cov_handle* h) {
 int hidden_reset(cov_handle* h, const int32_t* envs, int n) {
   if (!h->hidden) return GF_OK;
   hipError_t e = gf::launch_cov_hidden_reset(hidden_args(h), envs, n, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_hidden_reset_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_hidden_reset_kernel: ") + hipGetErrorString(e));
   return GF_OK;
 }
 
@@ -370,18 +341,18 @@ int hidden_reset(cov_handle* h, const int32_t* envs, int n) {
 int hidden_pass(cov_handle* h) {
   if (!h->hidden) return GF_OK;
   hipError_t e = gf::launch_cov_hidden(hidden_args(h), h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_hidden_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_hidden_kernel: ") + hipGetErrorString(e));
   return GF_OK;
 }
 
 // Device scratch of at least `bytes` (grown on demand, reused across calls).
 int scratch(cov_handle* h, size_t bytes, unsigned char** out) {
   if (bytes > h->scratch_bytes) {
-    if (h->scratch) CV_HIP(hipFree(h->scratch));
+    if (h->scratch) GF_HIP(hipFree(h->scratch));
     h->scratch = nullptr;
     h->scratch_bytes = 0;
     if (hipMalloc(reinterpret_cast<void**>(&h->scratch), bytes) != hipSuccess)
-      return cfail(GF_ENOMEM, "hipMalloc of wire-format scratch failed");
+      return fail(GF_ENOMEM, "hipMalloc of wire-format scratch failed");
     h->scratch_bytes = bytes;
   }
   *out = h->scratch;
@@ -406,11 +377,11 @@ void graph_sizes(const cov_handle* h, bool mask_all, const int32_t* keep, std::v
 int hidden_keep(cov_handle* h, std::vector<int32_t>& keep) {
   keep.clear();
   if (!h->hidden) return GF_OK;
-  if (!h->has_state) return cfail(GF_ESTATE, "hidden nodes: reset first (the edge counts follow the observation)");
+  if (!h->has_state) return fail(GF_ESTATE, "hidden nodes: reset first (the edge counts follow the observation)");
   if (int rc = use(h)) return rc;
   keep.resize(h->cfg.n_envs);
-  CV_HIP(hipMemcpyAsync(keep.data(), h->hnkeep, keep.size() * 4, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipMemcpyAsync(keep.data(), h->hnkeep, keep.size() * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
@@ -427,12 +398,12 @@ double py_floordiv(double a, double b) {
 }
 
 int check_map_config(const cov_map_config* mc) {
-  if (!mc) return cfail(GF_EINVAL, "null map configuration");
-  if (!(mc->x_max > mc->x_min) || !(mc->y_max > mc->y_min)) return cfail(GF_EINVAL, "map: empty arena");
+  if (!mc) return fail(GF_EINVAL, "null map configuration");
+  if (!(mc->x_max > mc->x_min) || !(mc->y_max > mc->y_min)) return fail(GF_EINVAL, "map: empty arena");
   if (!(mc->lattice_spacing > 0) || !(mc->world_radius > 0) || !(mc->road_radius > 0) || !(mc->near_radius > 0) ||
       !(mc->link_radius > 0))
-    return cfail(GF_EINVAL, "map: spacing and radii must be positive");
-  if (mc->n_cities < 3 || mc->n_cities > gf::kMapMaxCities) return cfail(GF_EINVAL, "map: n_cities must be in [3, 32]");
+    return fail(GF_EINVAL, "map: spacing and radii must be positive");
+  if (mc->n_cities < 3 || mc->n_cities > gf::kMapMaxCities) return fail(GF_EINVAL, "map: n_cities must be in [3, 32]");
   return GF_OK;
 }
 
@@ -472,21 +443,21 @@ int ensure_lattice(cov_handle* h, const cov_map_config* mc) {
   int NI = 0, NJ = 0;
   build_lattice(mc, xy, cell, &NI, &NJ);
   const int L = static_cast<int>(cell.size());
-  if (L < 1) return cfail(GF_EINVAL, "map: the lattice has no point in the arena");
-  if ((size_t)NI * NJ > (size_t)1 << 26) return cfail(GF_EINVAL, "map: lattice grid too large");
+  if (L < 1) return fail(GF_EINVAL, "map: the lattice has no point in the arena");
+  if ((size_t)NI * NJ > (size_t)1 << 26) return fail(GF_EINVAL, "map: lattice grid too large");
   for (void* p : {static_cast<void*>(h->lat), static_cast<void*>(h->lat_cell), static_cast<void*>(h->lat_grid)})
-    if (p) CV_HIP(hipFree(p));
+    if (p) GF_HIP(hipFree(p));
   h->lat = nullptr;
   h->lat_cell = h->lat_grid = nullptr;
   std::vector<int32_t> grid((size_t)NI * NJ, -1);
   for (int l = 0; l < L; ++l) grid[cell[l]] = l;
   int rc;
-  if ((rc = calloc_dev(&h->lat, (size_t)L)) || (rc = calloc_dev(&h->lat_cell, (size_t)L)) ||
-      (rc = calloc_dev(&h->lat_grid, (size_t)NI * NJ)))
+  if ((rc = dalloc_zero(&h->lat, (size_t)L)) || (rc = dalloc_zero(&h->lat_cell, (size_t)L)) ||
+      (rc = dalloc_zero(&h->lat_grid, (size_t)NI * NJ)))
     return rc;
-  CV_HIP(hipMemcpy(h->lat, xy.data(), (size_t)L * 16, hipMemcpyHostToDevice));
-  CV_HIP(hipMemcpy(h->lat_cell, cell.data(), (size_t)L * 4, hipMemcpyHostToDevice));
-  CV_HIP(hipMemcpy(h->lat_grid, grid.data(), grid.size() * 4, hipMemcpyHostToDevice));
+  GF_HIP(hipMemcpy(h->lat, xy.data(), (size_t)L * 16, hipMemcpyHostToDevice));
+  GF_HIP(hipMemcpy(h->lat_cell, cell.data(), (size_t)L * 4, hipMemcpyHostToDevice));
+  GF_HIP(hipMemcpy(h->lat_grid, grid.data(), grid.size() * 4, hipMemcpyHostToDevice));
   h->lat_L = L;
   h->lat_NI = NI;
   h->lat_NJ = NJ;
@@ -499,9 +470,9 @@ int ensure_map_buffers(cov_handle* h) {
   if (h->map_cities) return GF_OK;
   const size_t B = h->cfg.n_envs;
   int rc;
-  if ((rc = calloc_dev(&h->map_key, B * gf::kMtN)) || (rc = calloc_dev(&h->map_pos, B)) ||
-      (rc = calloc_dev(&h->map_cities, B * gf::kMapMaxCities * 2)) || (rc = calloc_dev(&h->map_nraw, B)) ||
-      (rc = calloc_dev(&h->map_status, B)))
+  if ((rc = dalloc_zero(&h->map_key, B * gf::kMtN)) || (rc = dalloc_zero(&h->map_pos, B)) ||
+      (rc = dalloc_zero(&h->map_cities, B * gf::kMapMaxCities * 2)) || (rc = dalloc_zero(&h->map_nraw, B)) ||
+      (rc = dalloc_zero(&h->map_status, B)))
     return rc;
   return GF_OK;
 }
@@ -510,7 +481,7 @@ int put(cov_handle* h, void* dst, const void* src, size_t bytes, bool dev_dst, b
   if (!dst || !bytes) return GF_OK;
   const hipMemcpyKind k = dev_dst ? (dev_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)
                                   : (dev_src ? hipMemcpyDeviceToHost : hipMemcpyHostToHost);
-  CV_HIP(hipMemcpyAsync(dst, src, bytes, k, h->stream));
+  GF_HIP(hipMemcpyAsync(dst, src, bytes, k, h->stream));
   return GF_OK;
 }
 
@@ -519,17 +490,14 @@ int put(cov_handle* h, void* dst, const void* src, size_t bytes, bool dev_dst, b
 extern "C" {
 
 int cov_create(const cov_config* cfg, cov_handle** out) {
-  if (!cfg || !out) return cfail(GF_EINVAL, "null argument");
+  if (!cfg || !out) return fail(GF_EINVAL, "null argument");
   *out = nullptr;
   if (cfg->n_robots < 1 || cfg->n_envs < 1 || cfg->max_nodes <= cfg->n_robots)
-    return cfail(GF_EINVAL, "need n_robots >= 1, n_envs >= 1, max_nodes > n_robots");
-  if (cfg->n_robots > 4096) return cfail(GF_EINVAL, "n_robots > 4096 not supported");
-  if (!(cfg->res > 0) || !(cfg->motion_radius > 0)) return cfail(GF_EINVAL, "bad res/motion_radius");
-  if (cfg->horizon < -1) return cfail(GF_EINVAL, "horizon must be >= -1");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return cfail(GF_EHIP, "no HIP device available (libgymflock needs an MI355X)");
-  if (cfg->device < 0 || cfg->device >= ndev) return cfail(GF_EINVAL, "device ordinal out of range");
+    return fail(GF_EINVAL, "need n_robots >= 1, n_envs >= 1, max_nodes > n_robots");
+  if (cfg->n_robots > 4096) return fail(GF_EINVAL, "n_robots > 4096 not supported");
+  if (!(cfg->res > 0) || !(cfg->motion_radius > 0)) return fail(GF_EINVAL, "bad res/motion_radius");
+  if (cfg->horizon < -1) return fail(GF_EINVAL, "horizon must be >= -1");
+  if (int rc = gf::select_device(cfg->device)) return rc;
   cov_handle* h = new cov_handle();
   h->cfg = *cfg;
   const size_t B = cfg->n_envs, R = cfg->n_robots, M = cfg->max_nodes, Tm = M - R, E = 4 * M;
@@ -542,22 +510,22 @@ int cov_create(const cov_config* cfg, cov_handle** out) {
   a.res = cfg->res;
   a.motion_radius = cfg->motion_radius;
   int rc = GF_OK;
-  if (hipSetDevice(cfg->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_s2, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming) != hipSuccess ||
       hipEventCreate(&h->tw[0]) != hipSuccess || hipEventCreate(&h->tw[1]) != hipSuccess) {
     cov_release(h);
-    return cfail(GF_EHIP, "stream create failed");
+    return fail(GF_EHIP, "stream create failed");
   }
-  if ((rc = calloc_dev(&h->ntg, B)) || (rc = calloc_dev(&h->tgt, B * Tm * 2)) || (rc = calloc_dev(&a.nbr, B * Tm * 4)) ||
-      (rc = calloc_dev(&a.cnt, B * Tm)) || (rc = calloc_dev(&a.n_motion, B)) || (rc = calloc_dev(&a.xr, B * R * 2)) ||
-      (rc = calloc_dev(&a.cur, B * R)) || (rc = calloc_dev(&a.visited, B * Tm)) || (rc = calloc_dev(&a.nvisited, B)) ||
-      (rc = calloc_dev(&a.step_counter, B)) || (rc = calloc_dev(&a.dirty, B)) || (rc = calloc_dev(&h->actions, B * R)) ||
-      (rc = calloc_dev(&a.reward, B)) || (rc = calloc_dev(&a.done, B)) || (rc = calloc_dev(&a.nodes, B * M * 3)) ||
-      (rc = calloc_dev(&a.edges, B * E)) || (rc = calloc_dev(&a.senders, B * E)) || (rc = calloc_dev(&a.receivers, B * E)) ||
-      (rc = calloc_dev(&a.obs_step, B)) || (rc = calloc_dev(&a.axy, B * Tm * 8)) || (rc = calloc_dev(&a.nrec, B * Tm * 16)) || (rc = calloc_dev(&h->err, 1)) || (rc = calloc_dev(&h->start, B * R)) ||
-      (rc = calloc_dev(&h->visited0, B * Tm)) || (rc = calloc_dev(&h->envsel, B))) {
+  if ((rc = dalloc_zero(&h->ntg, B)) || (rc = dalloc_zero(&h->tgt, B * Tm * 2)) || (rc = dalloc_zero(&a.nbr, B * Tm * 4)) ||
+      (rc = dalloc_zero(&a.cnt, B * Tm)) || (rc = dalloc_zero(&a.n_motion, B)) || (rc = dalloc_zero(&a.xr, B * R * 2)) ||
+      (rc = dalloc_zero(&a.cur, B * R)) || (rc = dalloc_zero(&a.visited, B * Tm)) || (rc = dalloc_zero(&a.nvisited, B)) ||
+      (rc = dalloc_zero(&a.step_counter, B)) || (rc = dalloc_zero(&a.dirty, B)) || (rc = dalloc_zero(&h->actions, B * R)) ||
+      (rc = dalloc_zero(&a.reward, B)) || (rc = dalloc_zero(&a.done, B)) || (rc = dalloc_zero(&a.nodes, B * M * 3)) ||
+      (rc = dalloc_zero(&a.edges, B * E)) || (rc = dalloc_zero(&a.senders, B * E)) || (rc = dalloc_zero(&a.receivers, B * E)) ||
+      (rc = dalloc_zero(&a.obs_step, B)) || (rc = dalloc_zero(&a.axy, B * Tm * 8)) || (rc = dalloc_zero(&a.nrec, B * Tm * 16)) || (rc = dalloc_zero(&h->err, 1)) || (rc = dalloc_zero(&h->start, B * R)) ||
+      (rc = dalloc_zero(&h->visited0, B * Tm)) || (rc = dalloc_zero(&h->envsel, B))) {
     cov_release(h);
     return rc;
   }
@@ -577,28 +545,28 @@ int cov_destroy(cov_handle* h) {
 }
 
 int cov_set_targets(cov_handle* h, int env, int n_targets, const double* targets) {
-  if (!h || !targets) return cfail(GF_EINVAL, "null argument");
+  if (!h || !targets) return fail(GF_EINVAL, "null argument");
   const int B = h->cfg.n_envs, Tm = h->a.Tmax;
-  if (env >= B) return cfail(GF_EINVAL, "env index out of range");
+  if (env >= B) return fail(GF_EINVAL, "env index out of range");
   if (n_targets < 1 || n_targets > Tm)
-    return cfail(GF_EINVAL, "n_targets must be in [1, max_nodes - n_robots] (PAD_NODES, coverage.py:540-543)");
-  if (n_targets < h->cfg.n_robots) return cfail(GF_EINVAL, "fewer targets than robots (reset draws distinct starts)");
+    return fail(GF_EINVAL, "n_targets must be in [1, max_nodes - n_robots] (PAD_NODES, coverage.py:540-543)");
+  if (n_targets < h->cfg.n_robots) return fail(GF_EINVAL, "fewer targets than robots (reset draws distinct starts)");
   if (int rc = use(h)) return rc;
   const int b0 = env < 0 ? 0 : env, b1 = env < 0 ? B : env + 1;
   std::vector<int32_t> sel;
   for (int b = b0; b < b1; ++b) {
-    CV_HIP(hipMemcpyAsync(h->tgt + (size_t)b * Tm * 2, targets, (size_t)n_targets * 2 * sizeof(double),
+    GF_HIP(hipMemcpyAsync(h->tgt + (size_t)b * Tm * 2, targets, (size_t)n_targets * 2 * sizeof(double),
                           hipMemcpyHostToDevice, h->stream));
     h->ntg_host[b] = n_targets;
     sel.push_back(b);
   }
-  CV_HIP(hipMemcpyAsync(h->ntg, h->ntg_host.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-  CV_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->ntg, h->ntg_host.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   hipError_t e = gf::launch_cov_graph(h->a, h->envsel, (int)sel.size(), h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
   if (int rc = hidden_reset(h, h->envsel, (int)sel.size())) return rc;
   if (int rc = check_err(h)) return rc;
-  CV_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  GF_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
   for (int b = b0; b < b1; ++b) h->tm_valid[b] = 0;
   h->tm_ready = false;
   h->has_graph = true;
@@ -607,7 +575,7 @@ int cov_set_targets(cov_handle* h, int env, int n_targets, const double* targets
 }
 
 int cov_map_lattice(const cov_map_config* mc, double* xy, int32_t* n) {
-  if (!n) return cfail(GF_EINVAL, "null count");
+  if (!n) return fail(GF_EINVAL, "null count");
   if (int rc = check_map_config(mc)) return rc;
   std::vector<double> pts;
   std::vector<int32_t> cell;
@@ -616,24 +584,24 @@ int cov_map_lattice(const cov_map_config* mc, double* xy, int32_t* n) {
   const int32_t cap = *n;
   *n = static_cast<int32_t>(cell.size());
   if (!xy) return GF_OK;
-  if (cap < *n) return cfail(GF_EINVAL, "lattice: the output holds fewer points than the lattice has");
+  if (cap < *n) return fail(GF_EINVAL, "lattice: the output holds fewer points than the lattice has");
   std::memcpy(xy, pts.data(), pts.size() * sizeof(double));
   return GF_OK;
 }
 
 int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t map_seed, const double* cities,
                       int flags, int32_t* n_targets_out, int32_t* status_out, double* cities_out) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
+  if (!h) return fail(GF_EINVAL, "null handle");
   if (int rc = check_map_config(mc)) return rc;
-  if (flags & ~(COV_MAP_SEED | COV_MAP_CITIES)) return cfail(GF_EINVAL, "flags: COV_MAP_SEED | COV_MAP_CITIES");
+  if (flags & ~(COV_MAP_SEED | COV_MAP_CITIES)) return fail(GF_EINVAL, "flags: COV_MAP_SEED | COV_MAP_CITIES");
   const bool given = flags & COV_MAP_CITIES;
-  if (given && !cities) return cfail(GF_EINVAL, "COV_MAP_CITIES needs the cities");
+  if (given && !cities) return fail(GF_EINVAL, "COV_MAP_CITIES needs the cities");
   const int B = h->cfg.n_envs, NC = mc->n_cities;
-  if (env >= B) return cfail(GF_EINVAL, "env index out of range");
+  if (env >= B) return fail(GF_EINVAL, "env index out of range");
   if (!given && (flags & COV_MAP_SEED) && map_seed + (uint64_t)B > 0x100000000ull)
-    return cfail(GF_EINVAL, "map_seed + n_envs must fit in 32 bits (np.random.seed)");
+    return fail(GF_EINVAL, "map_seed + n_envs must fit in 32 bits (np.random.seed)");
   if (!given && !(flags & COV_MAP_SEED) && !h->map_seeded)
-    return cfail(GF_ESTATE, "the envs' map streams were never seeded (COV_MAP_SEED)");
+    return fail(GF_ESTATE, "the envs' map streams were never seeded (COV_MAP_SEED)");
   if (int rc = use(h)) return rc;
   int rc;
   if ((rc = ensure_map_buffers(h))) return rc;
@@ -643,7 +611,7 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
   const double diag = 2.0 * std::sqrt(2.0) * mc->world_radius;
   const double wbound = NC + (3.0 * NC - 6.0) * (std::floor(diag / mc->road_radius) + 1.0);
   const size_t lds_max = 150 * 1024, lds_lat = (size_t)h->lat_L * 12;
-  if (lds_lat + 64 * 16 > lds_max) return cfail(GF_EINVAL, "map: lattice too large for the LDS");
+  if (lds_lat + 64 * 16 > lds_max) return fail(GF_EINVAL, "map: lattice too large for the LDS");
   // the waypoint grid of the near-road test: cells of side near_radius (1 + 2^-20) over the
   // cities' square and the arena, one cell of margin; without room for it (or for an odd
   // configuration), every lattice point scans every waypoint
@@ -658,7 +626,7 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
   const int b0 = env < 0 ? 0 : env, b1 = env < 0 ? B : env + 1, nsel = b1 - b0;
   std::vector<int32_t> sel;
   for (int b = b0; b < b1; ++b) sel.push_back(b);
-  CV_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, h->stream));
   gf::CovMapArgs m{};
   m.n_sel = nsel;
   m.envs = h->envsel;
@@ -693,27 +661,27 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
   m.status = h->map_status;
   hipError_t e = hipSuccess;
   if (given) {
-    CV_HIP(hipMemcpy2DAsync(h->map_cities + (size_t)b0 * gf::kMapMaxCities * 2, gf::kMapMaxCities * 16, cities,
+    GF_HIP(hipMemcpy2DAsync(h->map_cities + (size_t)b0 * gf::kMapMaxCities * 2, gf::kMapMaxCities * 16, cities,
                             (size_t)NC * 16, (size_t)NC * 16, nsel, hipMemcpyHostToDevice, h->stream));
   } else {
     e = gf::launch_cov_map_cities(m, h->stream);
-    if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_map_cities_kernel: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_map_cities_kernel: ") + hipGetErrorString(e));
     if (flags & COV_MAP_SEED) h->map_seeded = true;
   }
   e = gf::launch_cov_map(m, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_map_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_map_kernel: ") + hipGetErrorString(e));
   e = gf::launch_cov_graph(h->a, h->envsel, nsel, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
   if (int rc3 = hidden_reset(h, h->envsel, nsel)) return rc3;
   std::vector<int32_t> nraw(nsel), st(nsel), ntg(B);
-  CV_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipMemcpyAsync(st.data(), h->map_status + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipMemcpyAsync(ntg.data(), h->ntg, B * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(st.data(), h->map_status + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(ntg.data(), h->ntg, B * 4, hipMemcpyDeviceToHost, h->stream));
   if (cities_out)
-    CV_HIP(hipMemcpy2DAsync(cities_out, (size_t)NC * 16, h->map_cities + (size_t)b0 * gf::kMapMaxCities * 2,
+    GF_HIP(hipMemcpy2DAsync(cities_out, (size_t)NC * 16, h->map_cities + (size_t)b0 * gf::kMapMaxCities * 2,
                             gf::kMapMaxCities * 16, (size_t)NC * 16, nsel, hipMemcpyDeviceToHost, h->stream));
   if (int rc2 = check_err(h)) return rc2;  // synchronises; motion-graph errors (degree > 4, edges)
-  CV_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  GF_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
   std::string bad;
   for (int k = 0; k < nsel; ++k) {
     const int b = b0 + k;
@@ -735,17 +703,17 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
   h->tm_ready = false;
   h->has_graph = true;
   for (int b = 0; b < B; ++b) h->has_graph = h->has_graph && h->ntg_host[b] > 0;
-  if (!bad.empty()) return cfail(GF_EINVAL, "cov_generate_maps: " + bad);
+  if (!bad.empty()) return fail(GF_EINVAL, "cov_generate_maps: " + bad);
   return GF_OK;
 }
 
 int cov_get_targets(cov_handle* h, int env, double* targets) {
-  if (!h || !targets || env < 0 || env >= h->cfg.n_envs) return cfail(GF_EINVAL, "bad argument");
-  if (h->ntg_host[env] < 1) return cfail(GF_ESTATE, "the env has no target map");
+  if (!h || !targets || env < 0 || env >= h->cfg.n_envs) return fail(GF_EINVAL, "bad argument");
+  if (h->ntg_host[env] < 1) return fail(GF_ESTATE, "the env has no target map");
   if (int rc = use(h)) return rc;
-  CV_HIP(hipMemcpyAsync(targets, h->tgt + (size_t)env * h->a.Tmax * 2, (size_t)h->ntg_host[env] * 16,
+  GF_HIP(hipMemcpyAsync(targets, h->tgt + (size_t)env * h->a.Tmax * 2, (size_t)h->ntg_host[env] * 16,
                         hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
@@ -753,18 +721,18 @@ static_assert(COV_POOL_CAP == gf::kPoolCap && COV_MAP_NO_WINDOW == gf::kMapNoWin
 
 int cov_load_occupancy(cov_handle* h, const cov_occupancy_config* oc, const uint8_t* grid, int n0, int n1,
                        int32_t* n_pool_out) {
-  if (!h || !oc || !grid) return cfail(GF_EINVAL, "null argument");
-  if (n0 < 1 || n1 < 1 || (int64_t)n0 * n1 > (1 << 20)) return cfail(GF_EINVAL, "occupancy: grid must be 1 to 2^20 cells");
-  if (oc->downsample_rate < 1) return cfail(GF_EINVAL, "occupancy: downsample_rate must be >= 1");
+  if (!h || !oc || !grid) return fail(GF_EINVAL, "null argument");
+  if (n0 < 1 || n1 < 1 || (int64_t)n0 * n1 > (1 << 20)) return fail(GF_EINVAL, "occupancy: grid must be 1 to 2^20 cells");
+  if (oc->downsample_rate < 1) return fail(GF_EINVAL, "occupancy: downsample_rate must be >= 1");
   if (!(oc->perimeter_delta >= 0.0) || !std::isfinite(oc->perimeter_delta))
-    return cfail(GF_EINVAL, "occupancy: perimeter_delta must be finite and >= 0");
-  if (!std::isfinite(oc->xyz_min[0]) || !std::isfinite(oc->xyz_min[1])) return cfail(GF_EINVAL, "occupancy: xyz_min must be finite");
+    return fail(GF_EINVAL, "occupancy: perimeter_delta must be finite and >= 0");
+  if (!std::isfinite(oc->xyz_min[0]) || !std::isfinite(oc->xyz_min[1])) return fail(GF_EINVAL, "occupancy: xyz_min must be finite");
   if (!(oc->num_subgraphs > 0.0) || !std::isfinite(oc->num_subgraphs))
-    return cfail(GF_EINVAL, "occupancy: num_subgraphs must be > 0");
-  if (oc->min_targets < 1 || oc->max_tries < 1) return cfail(GF_EINVAL, "occupancy: min_targets and max_tries must be >= 1");
+    return fail(GF_EINVAL, "occupancy: num_subgraphs must be > 0");
+  if (oc->min_targets < 1 || oc->max_tries < 1) return fail(GF_EINVAL, "occupancy: min_targets and max_tries must be >= 1");
   const double res = 0.5 * oc->downsample_rate;
   const double kd = std::floor(h->cfg.motion_radius / res) + 1.0;
-  if (!(kd <= 16.0)) return cfail(GF_EINVAL, "occupancy: motion_radius spans more than 16 cells of 0.5 * downsample_rate");
+  if (!(kd <= 16.0)) return fail(GF_EINVAL, "occupancy: motion_radius spans more than 16 cells of 0.5 * downsample_rate");
   // an upper bound of the pool before any launch: free cells with an occupied cell within
   // floor(perimeter_delta) cells on both axes (the kernel applies the Euclidean test)
   const int KP = (int)std::min<double>(std::floor(oc->perimeter_delta), (double)std::max(n0, n1));
@@ -773,7 +741,7 @@ int cov_load_occupancy(cov_handle* h, const cov_occupancy_config* oc, const uint
     for (int j = 0; j < n1; ++j)
       sum[(size_t)(i + 1) * (n1 + 1) + j + 1] = (grid[(size_t)i * n1 + j] ? 1 : 0) + sum[(size_t)i * (n1 + 1) + j + 1] +
                                                 sum[(size_t)(i + 1) * (n1 + 1) + j] - sum[(size_t)i * (n1 + 1) + j];
-  if (sum.back() == 0) return cfail(GF_EINVAL, "occupancy: the grid has no occupied cell (from_occupancy's minimum is empty)");
+  if (sum.back() == 0) return fail(GF_EINVAL, "occupancy: the grid has no occupied cell (from_occupancy's minimum is empty)");
   int64_t bound = 0;
   for (int i = 0; i < n0; ++i)
     for (int j = 0; j < n1; ++j) {
@@ -784,24 +752,24 @@ int cov_load_occupancy(cov_handle* h, const cov_occupancy_config* oc, const uint
       bound += occ > 0 ? 1 : 0;
     }
   if (bound > gf::kPoolCap)
-    return cfail(GF_EINVAL, "occupancy: the grid may give " + std::to_string(bound) + " targets, more than the pool holds (" +
+    return fail(GF_EINVAL, "occupancy: the grid may give " + std::to_string(bound) + " targets, more than the pool holds (" +
                                 std::to_string(gf::kPoolCap) + ")");
   if (int rc = use(h)) return rc;
   int rc;
   if (!h->pool_xy) {
-    if ((rc = calloc_dev(&h->pool_rawcell, (size_t)gf::kPoolCap)) || (rc = calloc_dev(&h->pool_raw, (size_t)gf::kPoolCap)) ||
-        (rc = calloc_dev(&h->pool_cell, (size_t)gf::kPoolCap)) || (rc = calloc_dev(&h->pool_info, (size_t)6)) ||
-        (rc = calloc_dev(&h->pool_counts, (size_t)3)) || (rc = calloc_dev(&h->sub_tries, (size_t)h->cfg.n_envs)) ||
-        (rc = calloc_dev(&h->pool_xy, (size_t)gf::kPoolCap)))
+    if ((rc = dalloc_zero(&h->pool_rawcell, (size_t)gf::kPoolCap)) || (rc = dalloc_zero(&h->pool_raw, (size_t)gf::kPoolCap)) ||
+        (rc = dalloc_zero(&h->pool_cell, (size_t)gf::kPoolCap)) || (rc = dalloc_zero(&h->pool_info, (size_t)6)) ||
+        (rc = dalloc_zero(&h->pool_counts, (size_t)3)) || (rc = dalloc_zero(&h->sub_tries, (size_t)h->cfg.n_envs)) ||
+        (rc = dalloc_zero(&h->pool_xy, (size_t)gf::kPoolCap)))
       return rc;
   }
   h->pool_loaded = false;
   for (void* p : {static_cast<void*>(h->occ_grid), static_cast<void*>(h->pool_cellmap)})
-    if (p) CV_HIP(hipFree(p));
+    if (p) GF_HIP(hipFree(p));
   h->occ_grid = nullptr;
   h->pool_cellmap = nullptr;
-  if ((rc = calloc_dev(&h->occ_grid, (size_t)n0 * n1)) || (rc = calloc_dev(&h->pool_cellmap, (size_t)n0 * n1))) return rc;
-  CV_HIP(hipMemcpyAsync(h->occ_grid, grid, (size_t)n0 * n1, hipMemcpyHostToDevice, h->stream));
+  if ((rc = dalloc_zero(&h->occ_grid, (size_t)n0 * n1)) || (rc = dalloc_zero(&h->pool_cellmap, (size_t)n0 * n1))) return rc;
+  GF_HIP(hipMemcpyAsync(h->occ_grid, grid, (size_t)n0 * n1, hipMemcpyHostToDevice, h->stream));
   gf::CovPoolArgs p{};
   p.n0 = n0;
   p.n1 = n1;
@@ -823,15 +791,15 @@ int cov_load_occupancy(cov_handle* h, const cov_occupancy_config* oc, const uint
   p.info = h->pool_info;
   p.counts = h->pool_counts;
   hipError_t e = gf::launch_cov_pool(p, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_pool_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_pool_kernel: ") + hipGetErrorString(e));
   int32_t counts[3] = {0, 0, 0};
-  CV_HIP(hipMemcpyAsync(counts, h->pool_counts, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipMemcpyAsync(h->pool_info_host, h->pool_info, sizeof(h->pool_info_host), hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
-  if (counts[2] || counts[1] > gf::kPoolCap) return cfail(GF_EINVAL, "occupancy: more targets than the pool holds");
-  if (counts[1] < 1) return cfail(GF_EINVAL, "occupancy: no free cell within perimeter_delta of an occupied one");
+  GF_HIP(hipMemcpyAsync(counts, h->pool_counts, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(h->pool_info_host, h->pool_info, sizeof(h->pool_info_host), hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
+  if (counts[2] || counts[1] > gf::kPoolCap) return fail(GF_EINVAL, "occupancy: more targets than the pool holds");
+  if (counts[1] < 1) return fail(GF_EINVAL, "occupancy: no free cell within perimeter_delta of an occupied one");
   h->pool_host.assign((size_t)counts[1] * 2, 0.0);
-  CV_HIP(hipMemcpy(h->pool_host.data(), h->pool_xy, (size_t)counts[1] * 16, hipMemcpyDeviceToHost));
+  GF_HIP(hipMemcpy(h->pool_host.data(), h->pool_xy, (size_t)counts[1] * 16, hipMemcpyDeviceToHost));
   h->occ = *oc;
   h->pool_n = counts[1];
   h->pool_n0 = n0;
@@ -843,8 +811,8 @@ int cov_load_occupancy(cov_handle* h, const cov_occupancy_config* oc, const uint
 }
 
 int cov_get_pool(cov_handle* h, double* targets, double* min_xy, double* max_xy, double* subgraph_size) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
-  if (!h->pool_loaded) return cfail(GF_ESTATE, "no target pool (cov_load_occupancy)");
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->pool_loaded) return fail(GF_ESTATE, "no target pool (cov_load_occupancy)");
   if (targets) std::memcpy(targets, h->pool_host.data(), h->pool_host.size() * sizeof(double));
   if (min_xy) std::memcpy(min_xy, h->pool_info_host, 16);
   if (max_xy) std::memcpy(max_xy, h->pool_info_host + 2, 16);
@@ -854,28 +822,28 @@ int cov_get_pool(cov_handle* h, double* targets, double* min_xy, double* max_xy,
 
 int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double* draws, int n_draws, int flags,
                          int32_t* n_targets_out, int32_t* status_out, int32_t* tries_out) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
-  if (flags & ~(COV_MAP_SEED | COV_MAP_DRAWS)) return cfail(GF_EINVAL, "flags: COV_MAP_SEED | COV_MAP_DRAWS");
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (flags & ~(COV_MAP_SEED | COV_MAP_DRAWS)) return fail(GF_EINVAL, "flags: COV_MAP_SEED | COV_MAP_DRAWS");
   const bool given = flags & COV_MAP_DRAWS;
-  if (given && !draws) return cfail(GF_EINVAL, "COV_MAP_DRAWS needs the draws");
-  if (given && n_draws < 1) return cfail(GF_EINVAL, "COV_MAP_DRAWS needs n_draws >= 1");
-  if (given && n_draws > (1 << 20)) return cfail(GF_EINVAL, "n_draws too large");
+  if (given && !draws) return fail(GF_EINVAL, "COV_MAP_DRAWS needs the draws");
+  if (given && n_draws < 1) return fail(GF_EINVAL, "COV_MAP_DRAWS needs n_draws >= 1");
+  if (given && n_draws > (1 << 20)) return fail(GF_EINVAL, "n_draws too large");
   const int B = h->cfg.n_envs;
-  if (env >= B) return cfail(GF_EINVAL, "env index out of range");
-  if (!h->pool_loaded) return cfail(GF_ESTATE, "no target pool (cov_load_occupancy)");
+  if (env >= B) return fail(GF_EINVAL, "env index out of range");
+  if (!h->pool_loaded) return fail(GF_ESTATE, "no target pool (cov_load_occupancy)");
   if (!(h->occ.num_subgraphs > 1.0))
-    return cfail(GF_EINVAL, "num_subgraphs <= 1 is not sampled: the map is the whole pool (cov_set_targets)");
+    return fail(GF_EINVAL, "num_subgraphs <= 1 is not sampled: the map is the whole pool (cov_set_targets)");
   if (!given && (flags & COV_MAP_SEED) && map_seed + (uint64_t)B > 0x100000000ull)
-    return cfail(GF_EINVAL, "map_seed + n_envs must fit in 32 bits (np.random.seed)");
+    return fail(GF_EINVAL, "map_seed + n_envs must fit in 32 bits (np.random.seed)");
   if (!given && !(flags & COV_MAP_SEED) && !h->map_seeded)
-    return cfail(GF_ESTATE, "the envs' map streams were never seeded (COV_MAP_SEED)");
-  if (gf::cov_submap_lds_bytes(h->pool_n) > 150 * 1024) return cfail(GF_EINVAL, "the pool is too large for the sampler's LDS");
+    return fail(GF_ESTATE, "the envs' map streams were never seeded (COV_MAP_SEED)");
+  if (gf::cov_submap_lds_bytes(h->pool_n) > 150 * 1024) return fail(GF_EINVAL, "the pool is too large for the sampler's LDS");
   if (int rc = use(h)) return rc;
   if (int rc = ensure_map_buffers(h)) return rc;
   const int b0 = env < 0 ? 0 : env, b1 = env < 0 ? B : env + 1, nsel = b1 - b0;
   std::vector<int32_t> sel;
   for (int b = b0; b < b1; ++b) sel.push_back(b);
-  CV_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, h->stream));
   const double* info = h->pool_info_host;
   gf::CovSubmapArgs m{};
   m.n_sel = nsel;
@@ -913,23 +881,23 @@ int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double
     unsigned char* d = nullptr;
     const size_t bytes = (size_t)nsel * n_draws * 16;
     if (int rc = scratch(h, bytes, &d)) return rc;
-    CV_HIP(hipMemcpyAsync(d, draws, bytes, hipMemcpyHostToDevice, h->stream));
+    GF_HIP(hipMemcpyAsync(d, draws, bytes, hipMemcpyHostToDevice, h->stream));
     m.draws = reinterpret_cast<const double*>(d);
   } else if (flags & COV_MAP_SEED) {
     h->map_seeded = true;
   }
   hipError_t e = gf::launch_cov_submap(m, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_submap_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_submap_kernel: ") + hipGetErrorString(e));
   e = gf::launch_cov_graph(h->a, h->envsel, nsel, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
   if (int rc3 = hidden_reset(h, h->envsel, nsel)) return rc3;
   std::vector<int32_t> nraw(nsel), st(nsel), tr(nsel), ntg(B);
-  CV_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipMemcpyAsync(st.data(), h->map_status + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipMemcpyAsync(tr.data(), h->sub_tries + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipMemcpyAsync(ntg.data(), h->ntg, B * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(st.data(), h->map_status + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(tr.data(), h->sub_tries + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(ntg.data(), h->ntg, B * 4, hipMemcpyDeviceToHost, h->stream));
   if (int rc2 = check_err(h)) return rc2;  // synchronises; motion-graph errors (degree > 4, edges)
-  CV_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  GF_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
   std::string bad;
   for (int k = 0; k < nsel; ++k) {
     const int b = b0 + k;
@@ -951,116 +919,116 @@ int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double
   h->tm_ready = false;
   h->has_graph = true;
   for (int b = 0; b < B; ++b) h->has_graph = h->has_graph && h->ntg_host[b] > 0;
-  if (!bad.empty()) return cfail(GF_EINVAL, "cov_generate_submaps: " + bad);
+  if (!bad.empty()) return fail(GF_EINVAL, "cov_generate_submaps: " + bad);
   return GF_OK;
 }
 
 int cov_reset(cov_handle* h, const int32_t* start, const uint8_t* visited) {
-  if (!h || !start || !visited) return cfail(GF_EINVAL, "null argument");
-  if (!h->has_graph) return cfail(GF_ESTATE, "set the target graph of every env first (cov_set_targets)");
+  if (!h || !start || !visited) return fail(GF_EINVAL, "null argument");
+  if (!h->has_graph) return fail(GF_ESTATE, "set the target graph of every env first (cov_set_targets)");
   const size_t B = h->cfg.n_envs, R = h->cfg.n_robots, Tm = h->a.Tmax;
   for (size_t b = 0; b < B; ++b)
     for (size_t i = 0; i < R; ++i)
-      if (start[b * R + i] < 0 || start[b * R + i] >= h->ntg_host[b]) return cfail(GF_EINVAL, "start target out of range");
+      if (start[b * R + i] < 0 || start[b * R + i] >= h->ntg_host[b]) return fail(GF_EINVAL, "start target out of range");
   if (int rc = use(h)) return rc;
-  CV_HIP(hipMemcpyAsync(h->start, start, B * R * 4, hipMemcpyHostToDevice, h->stream));
-  CV_HIP(hipMemcpyAsync(h->visited0, visited, B * Tm, hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->start, start, B * R * 4, hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->visited0, visited, B * Tm, hipMemcpyHostToDevice, h->stream));
   hipError_t e = gf::launch_cov_reset(h->a, h->start, h->visited0, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_reset_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_reset_kernel: ") + hipGetErrorString(e));
   if (int rc = hidden_reset(h, nullptr, (int)B)) return rc;
   gf::CovArgs a = h->a;
   a.actions = nullptr;
   e = gf::launch_cov_step(a, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
   if (int rc = hidden_pass(h)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   h->has_state = true;
   return GF_OK;
 }
 
 int cov_reset_seeded(cov_handle* h, uint64_t seed, double frac_active, int32_t* start_out, uint8_t* visited_out) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
-  if (!h->has_graph) return cfail(GF_ESTATE, "set the target graph of every env first (cov_set_targets)");
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_graph) return fail(GF_ESTATE, "set the target graph of every env first (cov_set_targets)");
   const size_t B = h->cfg.n_envs, R = h->cfg.n_robots, Tm = h->a.Tmax;
-  if (seed + B > 0x100000000ull) return cfail(GF_EINVAL, "seed + n_envs must fit in 32 bits (RandomState seeds)");
-  if (!(frac_active >= 0.0 && frac_active <= 1.0)) return cfail(GF_EINVAL, "frac_active must be in [0, 1]");
+  if (seed + B > 0x100000000ull) return fail(GF_EINVAL, "seed + n_envs must fit in 32 bits (RandomState seeds)");
+  if (!(frac_active >= 0.0 && frac_active <= 1.0)) return fail(GF_EINVAL, "frac_active must be in [0, 1]");
   if ((size_t)gf::kMtN * 4 + Tm * 5 > 65536)  // the draw kernel's LDS: key, permutation, flags
-    return cfail(GF_EINVAL, "max_nodes - n_robots too large for the device reset draws (draw on the host)");
+    return fail(GF_EINVAL, "max_nodes - n_robots too large for the device reset draws (draw on the host)");
   if (int rc = use(h)) return rc;
   if (!h->mt_key) {
     int rc;
-    if ((rc = calloc_dev(&h->mt_key, B * gf::kMtN)) || (rc = calloc_dev(&h->mt_pos, B))) return rc;
+    if ((rc = dalloc_zero(&h->mt_key, B * gf::kMtN)) || (rc = dalloc_zero(&h->mt_pos, B))) return rc;
   }
   gf::CovArgs a = h->a;
   a.mt_key = h->mt_key;
   a.mt_pos = h->mt_pos;
   hipError_t e = gf::launch_cov_seed_reset(a, static_cast<uint32_t>(seed), frac_active, h->start, h->visited0, h->stream);
   if (e == hipSuccess) e = gf::launch_cov_reset(h->a, h->start, h->visited0, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_reset_seeded: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_reset_seeded: ") + hipGetErrorString(e));
   if (int rc = hidden_reset(h, nullptr, (int)B)) return rc;
   a = h->a;
   a.actions = nullptr;
   e = gf::launch_cov_step(a, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
   if (int rc = hidden_pass(h)) return rc;
-  if (start_out) CV_HIP(hipMemcpyAsync(start_out, h->start, B * R * 4, hipMemcpyDeviceToHost, h->stream));
-  if (visited_out) CV_HIP(hipMemcpyAsync(visited_out, h->visited0, B * Tm, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  if (start_out) GF_HIP(hipMemcpyAsync(start_out, h->start, B * R * 4, hipMemcpyDeviceToHost, h->stream));
+  if (visited_out) GF_HIP(hipMemcpyAsync(visited_out, h->visited0, B * Tm, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   h->has_state = true;
   return GF_OK;
 }
 
 int cov_set_actions(cov_handle* h, const int32_t* actions) {
-  if (!h || !actions) return cfail(GF_EINVAL, "null argument");
+  if (!h || !actions) return fail(GF_EINVAL, "null argument");
   if (int rc = use(h)) return rc;
-  CV_HIP(hipMemcpyAsync(h->actions, actions, (size_t)h->cfg.n_envs * h->cfg.n_robots * 4, hipMemcpyHostToDevice,
+  GF_HIP(hipMemcpyAsync(h->actions, actions, (size_t)h->cfg.n_envs * h->cfg.n_robots * 4, hipMemcpyHostToDevice,
                         h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 int cov_set_rng(cov_handle* h, const uint32_t* keys, const int32_t* pos) {
-  if (!h || !keys || !pos) return cfail(GF_EINVAL, "null argument");
+  if (!h || !keys || !pos) return fail(GF_EINVAL, "null argument");
   const size_t B = h->cfg.n_envs;
   if (h->cfg.n_robots > gf::kMtN)
-    return cfail(GF_EINVAL, "device np_random draws need n_robots <= 624 (one key regeneration per step)");
+    return fail(GF_EINVAL, "device np_random draws need n_robots <= 624 (one key regeneration per step)");
   for (size_t b = 0; b < B; ++b)
-    if (pos[b] < 0 || pos[b] > gf::kMtN) return cfail(GF_EINVAL, "stream position outside [0, 624]");
+    if (pos[b] < 0 || pos[b] > gf::kMtN) return fail(GF_EINVAL, "stream position outside [0, 624]");
   if (int rc = use(h)) return rc;
   if (!h->mt_key) {
     int rc;
-    if ((rc = calloc_dev(&h->mt_key, B * gf::kMtN)) || (rc = calloc_dev(&h->mt_pos, B))) return rc;
+    if ((rc = dalloc_zero(&h->mt_key, B * gf::kMtN)) || (rc = dalloc_zero(&h->mt_pos, B))) return rc;
   }
-  CV_HIP(hipMemcpyAsync(h->mt_key, keys, B * gf::kMtN * 4, hipMemcpyHostToDevice, h->stream));
-  CV_HIP(hipMemcpyAsync(h->mt_pos, pos, B * 4, hipMemcpyHostToDevice, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipMemcpyAsync(h->mt_key, keys, B * gf::kMtN * 4, hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->mt_pos, pos, B * 4, hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 int cov_get_rng(cov_handle* h, uint32_t* keys, int32_t* pos) {
-  if (!h || !keys || !pos) return cfail(GF_EINVAL, "null argument");
-  if (!h->mt_key) return cfail(GF_ESTATE, "no np_random streams on the device (cov_set_rng)");
+  if (!h || !keys || !pos) return fail(GF_EINVAL, "null argument");
+  if (!h->mt_key) return fail(GF_ESTATE, "no np_random streams on the device (cov_set_rng)");
   if (int rc = use(h)) return rc;
   const size_t B = h->cfg.n_envs;
-  CV_HIP(hipMemcpyAsync(keys, h->mt_key, B * gf::kMtN * 4, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipMemcpyAsync(pos, h->mt_pos, B * 4, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipMemcpyAsync(keys, h->mt_key, B * gf::kMtN * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(pos, h->mt_pos, B * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 // n_steps fused greedy expert steps with the device fallback draws in one launch; equal to
 // n_steps calls of cov_step(h, NULL, COV_ACTIONS_GREEDY | COV_GREEDY_RNG).
 int cov_step_expert(cov_handle* h, int n_steps, double* rewards, uint8_t* done) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
-  if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
-  if (n_steps < 1) return cfail(GF_EINVAL, "n_steps must be at least 1");
-  if (h->hidden) return cfail(GF_EINVAL, std::string("cov_step_expert: ") + kHiddenFused);
-  if (!h->mt_key) return cfail(GF_ESTATE, "set the envs' np_random streams first (cov_set_rng or cov_reset_seeded)");
-  if (h->cfg.n_robots > gf::kMtN) return cfail(GF_EINVAL, "n_robots <= 624 (one key regeneration per step)");
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
+  if (n_steps < 1) return fail(GF_EINVAL, "n_steps must be at least 1");
+  if (h->hidden) return fail(GF_EINVAL, std::string("cov_step_expert: ") + kHiddenFused);
+  if (!h->mt_key) return fail(GF_ESTATE, "set the envs' np_random streams first (cov_set_rng or cov_reset_seeded)");
+  if (h->cfg.n_robots > gf::kMtN) return fail(GF_EINVAL, "n_robots <= 624 (one key regeneration per step)");
   if (int rc = use(h)) return rc;
   if (!h->tm_ready || !h->tm_glist)
     if (int rc = ensure_time_matrix(h)) return rc;
-  if (!h->tm_glist) return cfail(GF_EINVAL, "the fused expert needs max_nodes - n_robots <= 1024 (the greedy lists)");
+  if (!h->tm_glist) return fail(GF_EINVAL, "the fused expert needs max_nodes - n_robots <= 1024 (the greedy lists)");
   if (int rc = join_s2(h)) return rc;
   gf::CovArgsM m{};
   m.a = h->a;
@@ -1083,28 +1051,28 @@ int cov_step_expert(cov_handle* h, int n_steps, double* rewards, uint8_t* done) 
     m.done_k = buf + n * 8;
   }
   hipError_t e = gf::launch_cov_step_multi(m, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_multi_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_step_multi_kernel: ") + hipGetErrorString(e));
   h->main_dirty = true;
   h->other_work = true;
   if (!buf) return GF_OK;
   if (int rc = copy_out(h, rewards, m.reward_k, n * 8)) return rc;
   if (int rc = copy_out(h, done, m.done_k, n)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return check_err(h);
 }
 
 int cov_step(cov_handle* h, const int32_t* actions, int flags) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
-  if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
-  CV_HIP(hipSetDevice(h->cfg.device));
-  if ((flags & COV_ACTIONS_GREEDY) && h->hidden) return cfail(GF_EINVAL, std::string("COV_ACTIONS_GREEDY: ") + kHiddenFused);
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
+  GF_HIP(hipSetDevice(h->cfg.device));
+  if ((flags & COV_ACTIONS_GREEDY) && h->hidden) return fail(GF_EINVAL, std::string("COV_ACTIONS_GREEDY: ") + kHiddenFused);
   gf::CovArgs a = h->a;
   if ((flags & COV_GREEDY_RNG) && !(flags & COV_ACTIONS_GREEDY))
-    return cfail(GF_EINVAL, "COV_GREEDY_RNG needs COV_ACTIONS_GREEDY");
+    return fail(GF_EINVAL, "COV_GREEDY_RNG needs COV_ACTIONS_GREEDY");
   if ((flags & COV_GREEDY_RNG) && !h->mt_key)
-    return cfail(GF_ESTATE, "COV_GREEDY_RNG: set the envs' np_random streams first (cov_set_rng)");
+    return fail(GF_ESTATE, "COV_GREEDY_RNG: set the envs' np_random streams first (cov_set_rng)");
   if ((flags & COV_GREEDY_RNG) && h->cfg.n_robots > gf::kMtN)
-    return cfail(GF_EINVAL, "COV_GREEDY_RNG needs n_robots <= 624 (one key regeneration per step)");
+    return fail(GF_EINVAL, "COV_GREEDY_RNG needs n_robots <= 624 (one key regeneration per step)");
   if (flags & COV_ACTIONS_GREEDY) {
     // controller(greedy=True) in the step's own launch, from the greedy lists
     if (!h->tm_ready || !h->tm_glist) {
@@ -1113,7 +1081,7 @@ int cov_step(cov_handle* h, const int32_t* actions, int flags) {
     }
     if (!h->tm_glist) {  // Tmax > kGreedyListMaxT: the row-scan greedy kernel, then the step
       if (flags & COV_GREEDY_RNG)
-        return cfail(GF_EINVAL, "COV_GREEDY_RNG needs max_nodes - n_robots <= 1024 (the greedy lists)");
+        return fail(GF_EINVAL, "COV_GREEDY_RNG needs max_nodes - n_robots <= 1024 (the greedy lists)");
       if (int rc = cov_controller_greedy(h, nullptr, nullptr, nullptr)) return rc;
       return cov_step(h, nullptr, COV_ACTIONS_RESIDENT);
     }
@@ -1130,17 +1098,17 @@ int cov_step(cov_handle* h, const int32_t* actions, int flags) {
       a.mt_pos = h->mt_pos;
     }
   } else if (flags & COV_ACTIONS_DEVICE) {
-    if (!actions) return cfail(GF_EINVAL, "null action pointer");
+    if (!actions) return fail(GF_EINVAL, "null action pointer");
     a.actions = actions;
   } else if (flags & COV_ACTIONS_RESIDENT) {
     a.actions = h->actions;
   } else {
-    if (!actions) return cfail(GF_EINVAL, "null action pointer");
+    if (!actions) return fail(GF_EINVAL, "null action pointer");
     const size_t n = (size_t)h->cfg.n_envs * h->cfg.n_robots;
     for (size_t k = 0; k < n; ++k)
-      if (actions[k] < 0 || actions[k] >= 4) return cfail(GF_EINVAL, "action outside [0, 4) (coverage.py:189 index)");
+      if (actions[k] < 0 || actions[k] >= 4) return fail(GF_EINVAL, "action outside [0, 4) (coverage.py:189 index)");
     if (int rc = join_s2(h)) return rc;  // the previous second half may still read h->actions
-    CV_HIP(hipMemcpyAsync(h->actions, actions, n * 4, hipMemcpyHostToDevice, h->stream));
+    GF_HIP(hipMemcpyAsync(h->actions, actions, n * 4, hipMemcpyHostToDevice, h->stream));
     h->main_dirty = h->other_work = true;
     a.actions = h->actions;
   }
@@ -1148,8 +1116,8 @@ int cov_step(cov_handle* h, const int32_t* actions, int flags) {
   h->other_work = false;
   if (split) {
     if (h->main_dirty) {
-      CV_HIP(hipEventRecord(h->ev_main, h->stream));
-      CV_HIP(hipStreamWaitEvent(h->stream2, h->ev_main, 0));
+      GF_HIP(hipEventRecord(h->ev_main, h->stream));
+      GF_HIP(hipStreamWaitEvent(h->stream2, h->ev_main, 0));
       h->main_dirty = false;
     }
     gf::CovArgs a1 = a;
@@ -1158,7 +1126,7 @@ int cov_step(cov_handle* h, const int32_t* actions, int flags) {
     a1.B = h->a.B - a.B;
     hipError_t e = gf::launch_cov_step(a, h->stream);
     if (e == hipSuccess) e = gf::launch_cov_step(a1, h->stream2);
-    if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
     h->s2_pending = true;
     if (h->timing) h->tw_steps++;
     if (h->hidden) {  // one pass over every env on `stream`, behind both halves and ahead of the next ones
@@ -1167,7 +1135,7 @@ int cov_step(cov_handle* h, const int32_t* actions, int flags) {
       h->main_dirty = true;
     }
     if (!(flags & (COV_ACTIONS_DEVICE | COV_ACTIONS_RESIDENT | COV_ACTIONS_GREEDY)))
-      CV_HIP(hipStreamSynchronize(h->stream));
+      GF_HIP(hipStreamSynchronize(h->stream));
     return GF_OK;
   }
   if (int rc = join_s2(h)) return rc;
@@ -1178,21 +1146,21 @@ int cov_step(cov_handle* h, const int32_t* actions, int flags) {
     if (h->ev_used + 2 > h->ev.size()) {
       for (int k = 0; k < 64; ++k) {
         hipEvent_t ev;
-        CV_HIP(hipEventCreate(&ev));
+        GF_HIP(hipEventCreate(&ev));
         h->ev.push_back(ev);
       }
     }
-    CV_HIP(hipEventRecord(h->ev[h->ev_used], h->stream));
+    GF_HIP(hipEventRecord(h->ev[h->ev_used], h->stream));
   }
   hipError_t e = gf::launch_cov_step(a, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
   if (int rc = hidden_pass(h)) return rc;  // inside the sampled window: the step a hidden handle pays for
   if (sample) {
-    CV_HIP(hipEventRecord(h->ev[h->ev_used + 1], h->stream));
+    GF_HIP(hipEventRecord(h->ev[h->ev_used + 1], h->stream));
     h->ev_used += 2;
   }
   if (!(flags & (COV_ACTIONS_DEVICE | COV_ACTIONS_RESIDENT | COV_ACTIONS_GREEDY)))
-    CV_HIP(hipStreamSynchronize(h->stream));
+    GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
@@ -1218,15 +1186,15 @@ extern "C" {
 int cov_step_host(cov_handle* h, const int32_t* actions, float* nodes, float* edges, int32_t* senders,
                   int32_t* receivers, int64_t* step, double* reward, uint8_t* done, int32_t* closest,
                   int32_t* next_actions, uint8_t* needs_random, int flags) {
-  if (!h || !actions) return cfail(GF_EINVAL, "null argument");
-  if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
-  if (flags & ~COV_NEXT_GREEDY) return cfail(GF_EINVAL, "flags: 0 or COV_NEXT_GREEDY");
-  if (h->hidden) return cfail(GF_EINVAL, std::string("cov_step_host: ") + kHiddenFused);
+  if (!h || !actions) return fail(GF_EINVAL, "null argument");
+  if (!h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
+  if (flags & ~COV_NEXT_GREEDY) return fail(GF_EINVAL, "flags: 0 or COV_NEXT_GREEDY");
+  if (h->hidden) return fail(GF_EINVAL, std::string("cov_step_host: ") + kHiddenFused);
   const bool ng = flags & COV_NEXT_GREEDY;
-  if (!ng && (next_actions || needs_random)) return cfail(GF_EINVAL, "next_actions / needs_random need COV_NEXT_GREEDY");
+  if (!ng && (next_actions || needs_random)) return fail(GF_EINVAL, "next_actions / needs_random need COV_NEXT_GREEDY");
   const size_t B = h->cfg.n_envs, R = h->cfg.n_robots, M = h->cfg.max_nodes, E = 4 * M, n = B * R;
   for (size_t k = 0; k < n; ++k)
-    if (actions[k] < 0 || actions[k] >= 4) return cfail(GF_EINVAL, "action outside [0, 4) (coverage.py:189 index)");
+    if (actions[k] < 0 || actions[k] >= 4) return fail(GF_EINVAL, "action outside [0, 4) (coverage.py:189 index)");
   // one launch on the handle's stream after everything outstanding on both streams
   if (int rc = use(h)) return rc;
   gf::CovArgs a = h->a;
@@ -1234,7 +1202,7 @@ int cov_step_host(cov_handle* h, const int32_t* actions, float* nodes, float* ed
     if (!h->tm_ready || !h->tm_glist)
       if (int rc = ensure_time_matrix(h)) return rc;
     if (!h->tm_glist)
-      return cfail(GF_EINVAL, "COV_NEXT_GREEDY needs max_nodes - n_robots <= 1024 (the per-node greedy lists)");
+      return fail(GF_EINVAL, "COV_NEXT_GREEDY needs max_nodes - n_robots <= 1024 (the per-node greedy lists)");
     a.next_greedy = 1;
     a.glist = h->tm_glist;
     a.glen = h->tm_glen;
@@ -1260,7 +1228,7 @@ int cov_step_host(cov_handle* h, const int32_t* actions, float* nodes, float* ed
   if (!h->herr) {
     void* p = nullptr;
     if (hipHostMalloc(&p, std::max<size_t>(B, 16) * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-      return cfail(GF_ENOMEM, "hipHostMalloc (error words)");
+      return fail(GF_ENOMEM, "hipHostMalloc (error words)");
     h->herr = static_cast<int32_t*>(p);
   }
   std::memset(h->herr, 0, B * sizeof(int32_t));
@@ -1273,14 +1241,14 @@ int cov_step_host(cov_handle* h, const int32_t* actions, float* nodes, float* ed
                    (!next_actions || a.h_next) && (!needs_random || a.h_nrand);
   if (fin) {
     if (!h->fin_cnt) {
-      if (int rc = calloc_dev(&h->fin_cnt, 1)) return rc;
+      if (int rc = dalloc_zero(&h->fin_cnt, 1)) return rc;
       void* p = nullptr;
       if (hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-        return cfail(GF_ENOMEM, "hipHostMalloc (completion flag)");
+        return fail(GF_ENOMEM, "hipHostMalloc (completion flag)");
       h->fin_host = static_cast<int32_t*>(p);
       *h->fin_host = 0;
       h->fin_dev = cov_mapped(h->fin_host);
-      if (!h->fin_dev) return cfail(GF_EHIP, "completion flag: no mapped address");
+      if (!h->fin_dev) return fail(GF_EHIP, "completion flag: no mapped address");
     }
     a.fin.cnt = h->fin_cnt;
     a.fin.host = h->fin_dev;
@@ -1291,35 +1259,35 @@ int cov_step_host(cov_handle* h, const int32_t* actions, float* nodes, float* ed
   if (n * 4 <= (size_t)gf::kCovUInlineBytes) {
     e = gf::launch_cov_step_uin(a, actions, h->stream);  // actions in the kernel arguments
   } else {
-    CV_HIP(hipMemcpyAsync(h->actions, actions, n * 4, hipMemcpyHostToDevice, h->stream));
+    GF_HIP(hipMemcpyAsync(h->actions, actions, n * 4, hipMemcpyHostToDevice, h->stream));
     a.actions = h->actions;
     e = gf::launch_cov_step(a, h->stream);
   }
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_step_kernel: ") + hipGetErrorString(e));
   const gf::CovArgs& d = h->a;
-  if (nodes && !a.h_nodes) CV_HIP(hipMemcpyAsync(nodes, d.nodes, B * M * 3 * 4, hipMemcpyDeviceToHost, h->stream));
-  if (edges && !a.h_edges) CV_HIP(hipMemcpyAsync(edges, d.edges, B * E * 4, hipMemcpyDeviceToHost, h->stream));
-  if (senders && !a.h_senders) CV_HIP(hipMemcpyAsync(senders, d.senders, B * E * 4, hipMemcpyDeviceToHost, h->stream));
+  if (nodes && !a.h_nodes) GF_HIP(hipMemcpyAsync(nodes, d.nodes, B * M * 3 * 4, hipMemcpyDeviceToHost, h->stream));
+  if (edges && !a.h_edges) GF_HIP(hipMemcpyAsync(edges, d.edges, B * E * 4, hipMemcpyDeviceToHost, h->stream));
+  if (senders && !a.h_senders) GF_HIP(hipMemcpyAsync(senders, d.senders, B * E * 4, hipMemcpyDeviceToHost, h->stream));
   if (receivers && !a.h_receivers)
-    CV_HIP(hipMemcpyAsync(receivers, d.receivers, B * E * 4, hipMemcpyDeviceToHost, h->stream));
-  if (step && !a.h_step) CV_HIP(hipMemcpyAsync(step, d.obs_step, B * 8, hipMemcpyDeviceToHost, h->stream));
-  if (reward && !a.h_reward) CV_HIP(hipMemcpyAsync(reward, d.reward, B * 8, hipMemcpyDeviceToHost, h->stream));
-  if (done && !a.h_done) CV_HIP(hipMemcpyAsync(done, d.done, B, hipMemcpyDeviceToHost, h->stream));
-  if (closest && !a.h_closest) CV_HIP(hipMemcpyAsync(closest, d.cur, n * 4, hipMemcpyDeviceToHost, h->stream));
-  if (next_actions && !a.h_next) CV_HIP(hipMemcpyAsync(next_actions, h->actions, n * 4, hipMemcpyDeviceToHost, h->stream));
+    GF_HIP(hipMemcpyAsync(receivers, d.receivers, B * E * 4, hipMemcpyDeviceToHost, h->stream));
+  if (step && !a.h_step) GF_HIP(hipMemcpyAsync(step, d.obs_step, B * 8, hipMemcpyDeviceToHost, h->stream));
+  if (reward && !a.h_reward) GF_HIP(hipMemcpyAsync(reward, d.reward, B * 8, hipMemcpyDeviceToHost, h->stream));
+  if (done && !a.h_done) GF_HIP(hipMemcpyAsync(done, d.done, B, hipMemcpyDeviceToHost, h->stream));
+  if (closest && !a.h_closest) GF_HIP(hipMemcpyAsync(closest, d.cur, n * 4, hipMemcpyDeviceToHost, h->stream));
+  if (next_actions && !a.h_next) GF_HIP(hipMemcpyAsync(next_actions, h->actions, n * 4, hipMemcpyDeviceToHost, h->stream));
   if (needs_random && !a.h_nrand)
-    CV_HIP(hipMemcpyAsync(needs_random, h->needs_random, n, hipMemcpyDeviceToHost, h->stream));
+    GF_HIP(hipMemcpyAsync(needs_random, h->needs_random, n, hipMemcpyDeviceToHost, h->stream));
   if (fin) {
     const hipError_t q = gf::wait_done(h->fin_host, h->fin_seq, h->stream);
-    if (q == hipErrorUnknown) return cfail(GF_EHIP, "cov_step_host: the step finished without its completion flag");
-    if (q != hipSuccess) return cfail(GF_EHIP, std::string("cov_step_host: ") + hipGetErrorString(q));
+    if (q == hipErrorUnknown) return fail(GF_EHIP, "cov_step_host: the step finished without its completion flag");
+    if (q != hipSuccess) return fail(GF_EHIP, std::string("cov_step_host: ") + hipGetErrorString(q));
   } else {
     // spin on the stream: a drop-in step is latency-bound (a blocking wait's wake-up
     // costs a sizeable part of it)
     for (;;) {
       const hipError_t q = hipStreamQuery(h->stream);
       if (q == hipSuccess) break;
-      if (q != hipErrorNotReady) return cfail(GF_EHIP, std::string("cov_step_host: ") + hipGetErrorString(q));
+      if (q != hipErrorNotReady) return fail(GF_EHIP, std::string("cov_step_host: ") + hipGetErrorString(q));
     }
   }
   int err = 0;
@@ -1329,37 +1297,37 @@ int cov_step_host(cov_handle* h, const int32_t* actions, float* nodes, float* ed
 }
 
 int cov_kernel_timing(cov_handle* h, int enable, double* avg_ms, int64_t* launches) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
+  if (!h) return fail(GF_EINVAL, "null handle");
   if (int rc = use(h)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   if (enable >= 1) {  // start: time every enable-th step launch
     h->ev_used = 0;
     h->timing = true;
     h->timing_stride = enable;
     h->timing_count = 0;
     h->tw_steps = 0;  // split steps: one window, device time per step
-    CV_HIP(hipEventRecord(h->tw[0], h->stream));
+    GF_HIP(hipEventRecord(h->tw[0], h->stream));
     h->other_work = false;  // both streams idle: the first timed step splits like the rest
     return GF_OK;
   }
   if (h->tw_steps > 0) {
-    CV_HIP(hipEventRecord(h->tw[1], h->stream));
-    CV_HIP(hipEventSynchronize(h->tw[1]));
+    GF_HIP(hipEventRecord(h->tw[1], h->stream));
+    GF_HIP(hipEventSynchronize(h->tw[1]));
     float ms = 0;
-    CV_HIP(hipEventElapsedTime(&ms, h->tw[0], h->tw[1]));
+    GF_HIP(hipEventElapsedTime(&ms, h->tw[0], h->tw[1]));
     if (avg_ms) *avg_ms = ms / h->tw_steps;
     if (launches) *launches = h->tw_steps;
     if (enable == 0) h->timing = false;
     else {
       h->tw_steps = 0;
-      CV_HIP(hipEventRecord(h->tw[0], h->stream));
+      GF_HIP(hipEventRecord(h->tw[0], h->stream));
     }
     return GF_OK;
   }
   double tot = 0;
   for (size_t k = 0; k + 1 < h->ev_used; k += 2) {
     float ms = 0;
-    CV_HIP(hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
+    GF_HIP(hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
     tot += ms;
   }
   const int64_t n = (int64_t)(h->ev_used / 2);
@@ -1370,23 +1338,23 @@ int cov_kernel_timing(cov_handle* h, int enable, double* avg_ms, int64_t* launch
 }
 
 int cov_set_robot_positions(cov_handle* h, int env, const double* xr) {
-  if (!h || !xr || env < 0 || env >= h->cfg.n_envs) return cfail(GF_EINVAL, "bad argument");
-  if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
+  if (!h || !xr || env < 0 || env >= h->cfg.n_envs) return fail(GF_EINVAL, "bad argument");
+  if (!h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
   if (int rc = use(h)) return rc;
   const size_t R = h->cfg.n_robots;
   const uint8_t one = 1;
-  CV_HIP(hipMemcpyAsync(h->a.xr + env * R * 2, xr, R * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  CV_HIP(hipMemcpyAsync(h->a.dirty + env, &one, 1, hipMemcpyHostToDevice, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipMemcpyAsync(h->a.xr + env * R * 2, xr, R * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->a.dirty + env, &one, 1, hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 int cov_get_obs(cov_handle* h, int env, float* nodes, float* edges, int32_t* senders, int32_t* receivers,
                 int64_t* step) {
-  if (!h || env < 0 || env >= h->cfg.n_envs) return cfail(GF_EINVAL, "bad argument");
+  if (!h || env < 0 || env >= h->cfg.n_envs) return fail(GF_EINVAL, "bad argument");
   // before the first reset the arrays hold the graph's static part (the motion edges the
   // env's nearby-starts draw walks, coverage.py:655-673); the robots' part follows reset
-  if (!h->has_state && !h->has_graph) return cfail(GF_ESTATE, "set the targets (cov_set_targets) or reset first");
+  if (!h->has_state && !h->has_graph) return fail(GF_ESTATE, "set the targets (cov_set_targets) or reset first");
   if (int rc = use(h)) return rc;
   const size_t M = h->cfg.max_nodes, E = 4 * M;
   const gf::CovArgs& a = h->a;
@@ -1395,50 +1363,50 @@ int cov_get_obs(cov_handle* h, int env, float* nodes, float* edges, int32_t* sen
   if (int rc = copy_out(h, senders, a.senders + env * E, E * 4)) return rc;
   if (int rc = copy_out(h, receivers, a.receivers + env * E, E * 4)) return rc;
   if (int rc = copy_out(h, step, a.obs_step + env, 8)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return check_err(h);
 }
 
 int cov_get_rewards(cov_handle* h, double* reward, uint8_t* done) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
+  if (!h) return fail(GF_EINVAL, "null handle");
   if (int rc = use(h)) return rc;
   const size_t B = h->cfg.n_envs;
   if (int rc = copy_out(h, reward, h->a.reward, B * 8)) return rc;
   if (int rc = copy_out(h, done, h->a.done, B)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return check_err(h);
 }
 
 int cov_get_robots(cov_handle* h, int env, double* xr, int32_t* nodes) {
-  if (!h || env < 0 || env >= h->cfg.n_envs) return cfail(GF_EINVAL, "bad argument");
+  if (!h || env < 0 || env >= h->cfg.n_envs) return fail(GF_EINVAL, "bad argument");
   if (int rc = use(h)) return rc;
   const size_t R = h->cfg.n_robots;
   if (int rc = copy_out(h, xr, h->a.xr + env * R * 2, R * 16)) return rc;
   if (int rc = copy_out(h, nodes, h->a.cur + env * R, R * 4)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 int cov_get_visited(cov_handle* h, int env, uint8_t* visited) {
-  if (!h || !visited || env < 0 || env >= h->cfg.n_envs) return cfail(GF_EINVAL, "bad argument");
+  if (!h || !visited || env < 0 || env >= h->cfg.n_envs) return fail(GF_EINVAL, "bad argument");
   if (int rc = use(h)) return rc;
   const size_t Tm = h->a.Tmax;
   if (int rc = copy_out(h, visited, h->a.visited + env * Tm, Tm)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 int cov_get_n_motion(cov_handle* h, int32_t* n_motion) {
-  if (!h || !n_motion) return cfail(GF_EINVAL, "null argument");
+  if (!h || !n_motion) return fail(GF_EINVAL, "null argument");
   if (int rc = use(h)) return rc;
   if (int rc = copy_out(h, n_motion, h->a.n_motion, (size_t)h->cfg.n_envs * 4)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 int cov_controller_greedy(cov_handle* h, int32_t* actions, uint8_t* needs_random, int64_t* n_random) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
-  if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
   if (int rc = use(h)) return rc;
   if (int rc = ensure_time_matrix(h)) return rc;
   gf::CovGreedyArgs g{};
@@ -1468,7 +1436,7 @@ int cov_controller_greedy(cov_handle* h, int32_t* actions, uint8_t* needs_random
   g.glen = h->tm_glen;
   g.gstride = h->gstride;
   hipError_t e = gf::launch_cov_greedy(g, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_greedy_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_greedy_kernel: ") + hipGetErrorString(e));
   if (!actions && !needs_random && !n_random) return GF_OK;
   const size_t n = (size_t)a.B * a.R;
   std::vector<uint8_t> mask;
@@ -1479,7 +1447,7 @@ int cov_controller_greedy(cov_handle* h, int32_t* actions, uint8_t* needs_random
   }
   if (int rc = copy_out(h, actions, h->actions, n * 4)) return rc;
   if (int rc = copy_out(h, rnd, h->needs_random, n)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   if (n_random) {
     int64_t cnt = 0;
     for (size_t k = 0; k < n; ++k) cnt += rnd[k] ? 1 : 0;
@@ -1489,7 +1457,7 @@ int cov_controller_greedy(cov_handle* h, int32_t* actions, uint8_t* needs_random
 }
 
 int cov_get_actions(cov_handle* h, int32_t* actions, uint8_t* needs_random) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
+  if (!h) return fail(GF_EINVAL, "null handle");
   if (int rc = use(h)) return rc;
   const size_t n = (size_t)h->cfg.n_envs * h->cfg.n_robots;
   if (int rc = copy_out(h, actions, h->actions, n * 4)) return rc;
@@ -1500,21 +1468,21 @@ int cov_get_actions(cov_handle* h, int32_t* actions, uint8_t* needs_random) {
       std::memset(needs_random, 0, n);
     }
   }
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 int cov_get_time_matrix(cov_handle* h, int env, int32_t* cost, int32_t* prev) {
-  if (!h || env < 0 || env >= h->cfg.n_envs) return cfail(GF_EINVAL, "bad argument");
-  if (!h->has_graph) return cfail(GF_ESTATE, "set the target graph first (cov_set_targets)");
+  if (!h || env < 0 || env >= h->cfg.n_envs) return fail(GF_EINVAL, "bad argument");
+  if (!h->has_graph) return fail(GF_ESTATE, "set the target graph first (cov_set_targets)");
   if (int rc = use(h)) return rc;
   if (int rc = ensure_time_matrix(h)) return rc;
   const size_t Tm = h->a.Tmax, T = h->ntg_host[env];
   std::vector<uint16_t> c(Tm * Tm);
   std::vector<int16_t> p(Tm * Tm);
-  CV_HIP(hipMemcpyAsync(c.data(), h->tm_cost + env * Tm * Tm, Tm * Tm * 2, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipMemcpyAsync(p.data(), h->tm_prevT + env * Tm * Tm, Tm * Tm * 2, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipMemcpyAsync(c.data(), h->tm_cost + env * Tm * Tm, Tm * Tm * 2, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(p.data(), h->tm_prevT + env * Tm * Tm, Tm * Tm * 2, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   for (size_t i = 0; i < T; ++i)
     for (size_t j = 0; j < T; ++j) {
       if (cost) cost[i * T + j] = c[i * Tm + j] == 0xFFFF ? 1000 : c[i * Tm + j];
@@ -1524,8 +1492,8 @@ int cov_get_time_matrix(cov_handle* h, int env, int32_t* cost, int32_t* prev) {
 }
 
 int cov_get_flat_obs(cov_handle* h, void* dst, int flags) {
-  if (!h || !dst) return cfail(GF_EINVAL, "null argument");
-  if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
+  if (!h || !dst) return fail(GF_EINVAL, "null argument");
+  if (!h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
   if (int rc = use(h)) return rc;
   const bool f32 = flags & COV_FLAT_F32;
   const int nf = h->hidden ? 4 : 3;
@@ -1542,16 +1510,16 @@ int cov_get_flat_obs(cov_handle* h, void* dst, int flags) {
     fa.senders = h->hsenders;
   }
   hipError_t e = gf::launch_cov_flat_obs(fa, nf, out, f32, h->stream);
-  if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_flat_obs_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_flat_obs_kernel: ") + hipGetErrorString(e));
   if (flags & COV_OUT_DEVICE) return GF_OK;  // stream-ordered; cov_sync before reading
-  CV_HIP(hipMemcpyAsync(dst, out, bytes, hipMemcpyDeviceToHost, h->stream));
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipMemcpyAsync(dst, out, bytes, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return check_err(h);
 }
 
 int cov_graphs_tuple_sizes(cov_handle* h, int32_t* n_edge, int64_t* total_edges, int flags) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
-  if (!h->has_graph) return cfail(GF_ESTATE, "set the target graph first (cov_set_targets)");
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_graph) return fail(GF_ESTATE, "set the target graph first (cov_set_targets)");
   std::vector<int32_t> ne, keep;
   std::vector<int64_t> off;
   if (int rc = hidden_keep(h, keep)) return rc;
@@ -1563,10 +1531,10 @@ int cov_graphs_tuple_sizes(cov_handle* h, int32_t* n_edge, int64_t* total_edges,
 
 int cov_get_graphs_tuple(cov_handle* h, int32_t* n_node, float* nodes, int32_t* n_edge, float* edges,
                          int32_t* senders, int32_t* receivers, float* globs, int flags) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
-  if (!h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
   if ((edges != nullptr) != (senders != nullptr) || (edges != nullptr) != (receivers != nullptr))
-    return cfail(GF_EINVAL, "edges, senders and receivers go together (all or none)");
+    return fail(GF_EINVAL, "edges, senders and receivers go together (all or none)");
   if (int rc = use(h)) return rc;
   const bool dev = flags & COV_OUT_DEVICE;
   const int B = h->cfg.n_envs, M = h->cfg.max_nodes;
@@ -1577,8 +1545,8 @@ int cov_get_graphs_tuple(cov_handle* h, int32_t* n_node, float* nodes, int32_t* 
   const int64_t total = off.back();
   if (!h->goff)
     if (hipMalloc(reinterpret_cast<void**>(&h->goff), (B + 1) * sizeof(int64_t)) != hipSuccess)
-      return cfail(GF_ENOMEM, "hipMalloc of graph offsets failed");
-  CV_HIP(hipMemcpyAsync(h->goff, off.data(), (B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+      return fail(GF_ENOMEM, "hipMalloc of graph offsets failed");
+  GF_HIP(hipMemcpyAsync(h->goff, off.data(), (B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
   if (edges) {
     float* e_out = edges;
     int32_t *s_out = senders, *r_out = receivers;
@@ -1592,7 +1560,7 @@ int cov_get_graphs_tuple(cov_handle* h, int32_t* n_node, float* nodes, int32_t* 
     hipError_t e = h->hidden ? gf::launch_cov_hidden_graphs(hidden_args(h), h->a.edges, h->goff, flags & COV_MASK_ALL,
                                                             e_out, s_out, r_out, h->stream)
                              : gf::launch_cov_graphs(h->a, h->goff, flags & COV_MASK_ALL, e_out, s_out, r_out, h->stream);
-    if (e != hipSuccess) return cfail(GF_EHIP, std::string("cov_graphs_kernel: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_graphs_kernel: ") + hipGetErrorString(e));
     if (!dev) {
       if (int rc = put(h, edges, e_out, (size_t)total * 4, false, true)) return rc;
       if (int rc = put(h, senders, s_out, (size_t)total * 4, false, true)) return rc;
@@ -1607,25 +1575,25 @@ int cov_get_graphs_tuple(cov_handle* h, int32_t* n_node, float* nodes, int32_t* 
   std::vector<float> gl(B);
   if (globs) {
     std::vector<int64_t> st(B);
-    CV_HIP(hipMemcpyAsync(st.data(), h->a.obs_step, B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    CV_HIP(hipStreamSynchronize(h->stream));
+    GF_HIP(hipMemcpyAsync(st.data(), h->a.obs_step, B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    GF_HIP(hipStreamSynchronize(h->stream));
     for (int b = 0; b < B; ++b) gl[b] = static_cast<float>(st[b]);
     if (int rc = put(h, globs, gl.data(), B * sizeof(float), dev, false)) return rc;
   }
-  CV_HIP(hipStreamSynchronize(h->stream));  // host temporaries above
+  GF_HIP(hipStreamSynchronize(h->stream));  // host temporaries above
   return check_err(h);
 }
 
 int cov_set_streams(cov_handle* h, int n) {
-  if (!h || n < 0 || n > 2) return cfail(GF_EINVAL, "n must be 0 (auto), 1 or 2");
+  if (!h || n < 0 || n > 2) return fail(GF_EINVAL, "n must be 0 (auto), 1 or 2");
   if (int rc = use(h)) return rc;
   h->nsplit = n;
   return GF_OK;
 }
 
 int cov_set_hidden(cov_handle* h, int enable) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
-  if (enable != 0 && enable != 1) return cfail(GF_EINVAL, "enable must be 0 or 1");
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (enable != 0 && enable != 1) return fail(GF_EINVAL, "enable must be 0 or 1");
   if (int rc = use(h)) return rc;
   if (!enable) {
     h->hidden = false;
@@ -1633,12 +1601,12 @@ int cov_set_hidden(cov_handle* h, int enable) {
   }
   const size_t B = h->cfg.n_envs, M = h->cfg.max_nodes, Tm = h->a.Tmax;
   if (gf::cov_hidden_lds_bytes(h->cfg.n_robots, h->cfg.max_nodes) > 64 * 1024)
-    return cfail(GF_EINVAL, "hidden nodes: n_robots * 16 + max_nodes / 4 bytes exceed the pass's 64 KB of LDS");
+    return fail(GF_EINVAL, "hidden nodes: n_robots * 16 + max_nodes / 4 bytes exceed the pass's 64 KB of LDS");
   if (!h->discovered) {
     int rc;
-    if ((rc = calloc_dev(&h->discovered, B * M)) || (rc = calloc_dev(&h->hnodes, B * M * 4)) ||
-        (rc = calloc_dev(&h->hsenders, B * 4 * M)) || (rc = calloc_dev(&h->gmask, B * Tm)) ||
-        (rc = calloc_dev(&h->ngmask, B)) || (rc = calloc_dev(&h->hnkeep, B)))
+    if ((rc = dalloc_zero(&h->discovered, B * M)) || (rc = dalloc_zero(&h->hnodes, B * M * 4)) ||
+        (rc = dalloc_zero(&h->hsenders, B * 4 * M)) || (rc = dalloc_zero(&h->gmask, B * Tm)) ||
+        (rc = dalloc_zero(&h->ngmask, B)) || (rc = dalloc_zero(&h->hnkeep, B)))
       return rc;
   }
   h->hidden = true;
@@ -1646,27 +1614,27 @@ int cov_set_hidden(cov_handle* h, int enable) {
   // an observation taken before this call gets its hidden form at once
   if (h->has_state)
     if (int rc = hidden_pass(h)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 int cov_get_hidden_obs(cov_handle* h, int env, float* nodes4, int32_t* senders, uint8_t* discovered) {
-  if (!h || env < 0 || env >= h->cfg.n_envs) return cfail(GF_EINVAL, "bad argument");
-  if (!h->hidden) return cfail(GF_ESTATE, "the handle does not hide nodes (cov_set_hidden)");
-  if ((nodes4 || senders) && !h->has_state) return cfail(GF_ESTATE, "reset first (cov_reset)");
+  if (!h || env < 0 || env >= h->cfg.n_envs) return fail(GF_EINVAL, "bad argument");
+  if (!h->hidden) return fail(GF_ESTATE, "the handle does not hide nodes (cov_set_hidden)");
+  if ((nodes4 || senders) && !h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
   if (int rc = use(h)) return rc;
   const size_t M = h->cfg.max_nodes;
   if (int rc = copy_out(h, nodes4, h->hnodes + env * M * 4, M * 4 * 4)) return rc;
   if (int rc = copy_out(h, senders, h->hsenders + env * M * 4, M * 4 * 4)) return rc;
   if (int rc = copy_out(h, discovered, h->discovered + env * M, M)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return check_err(h);
 }
 
 int cov_sync(cov_handle* h) {
-  if (!h) return cfail(GF_EINVAL, "null handle");
+  if (!h) return fail(GF_EINVAL, "null handle");
   if (int rc = use(h)) return rc;
-  CV_HIP(hipStreamSynchronize(h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   // both streams idle: the next step may split. main_dirty stays set (use_dev): reads of
   // the outputs a zero-copy consumer enqueues on `stream` after this call come before
   // the next step's second half
@@ -1675,14 +1643,3 @@ int cov_sync(cov_handle* h) {
 }
 
 }  // extern "C"
-
-// coverage_arl.hip is a source of its own in this directory's Makefile (GF_ARL_OWN_TU). A
-// build that lists the library's sources without it (the host-sanitizer build of the
-// C-ABI, tests/asan) gets its kernels and launchers here, with this file's flags.
-#ifndef GF_ARL_OWN_TU
-#include "coverage_arl.hip"
-#endif
-// coverage_hidden.hip likewise (GF_HIDDEN_OWN_TU)
-#ifndef GF_HIDDEN_OWN_TU
-#include "coverage_hidden.hip"
-#endif

@@ -20,11 +20,9 @@
 #include <cstdint>
 #include <string>
 
-#include "gymflock.h"
+#include "capi_common.h"
 
-namespace gf {
-int set_error(int code, const std::string& msg);
-}
+using gf::fail;
 
 namespace {
 
@@ -244,14 +242,6 @@ __global__ __launch_bounds__(kGuThreads) void gu_knn_fill_kernel(GuArgs a) {
   }
 }
 
-int gfail(int code, const std::string& m) { return gf::set_error(code, m); }
-
-#define GU_HIP(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) return gfail(GF_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 }  // namespace
 
 struct gu_graph {
@@ -271,10 +261,10 @@ template <class T>
 int grow(gu_graph* g, int slot, size_t n, T** out) {
   const size_t bytes = (n ? n : 1) * sizeof(T);
   if (g->cap[slot] < bytes) {
-    if (g->buf[slot]) GU_HIP(hipFree(g->buf[slot]));
+    if (g->buf[slot]) GF_HIP(hipFree(g->buf[slot]));
     g->buf[slot] = nullptr;
     g->cap[slot] = 0;
-    if (hipMalloc(&g->buf[slot], bytes) != hipSuccess) return gfail(GF_ENOMEM, "hipMalloc (graph helpers)");
+    if (hipMalloc(&g->buf[slot], bytes) != hipSuccess) return fail(GF_ENOMEM, "hipMalloc (graph helpers)");
     g->cap[slot] = bytes;
   }
   *out = static_cast<T*>(g->buf[slot]);
@@ -289,10 +279,10 @@ int grow(gu_graph* g, int slot, size_t n, T** out) {
 
 // common setup: positions to the device, the argument block
 int stage(gu_graph* g, const double* pos1, int32_t n1, const double* pos2, int32_t n2) {
-  if (!g) return gfail(GF_EINVAL, "null graph context");
-  if (n1 < 0 || (pos2 && n2 < 0)) return gfail(GF_EINVAL, "negative point count");
-  if (n1 > 0 && !pos1) return gfail(GF_EINVAL, "null positions");
-  GU_HIP(hipSetDevice(g->device));
+  if (!g) return fail(GF_EINVAL, "null graph context");
+  if (n1 < 0 || (pos2 && n2 < 0)) return fail(GF_EINVAL, "negative point count");
+  if (n1 > 0 && !pos1) return fail(GF_EINVAL, "null positions");
+  GF_HIP(hipSetDevice(g->device));
   GuArgs& a = g->a;
   a = GuArgs{};
   a.n1 = n1;
@@ -301,12 +291,12 @@ int stage(gu_graph* g, const double* pos1, int32_t n1, const double* pos2, int32
   double* d1 = nullptr;
   double* d2 = nullptr;
   GU_TRY(grow(g, B_P1, (size_t)2 * a.n1, &d1));
-  if (a.n1) GU_HIP(hipMemcpyAsync(d1, pos1, sizeof(double) * 2 * a.n1, hipMemcpyHostToDevice, g->stream));
+  if (a.n1) GF_HIP(hipMemcpyAsync(d1, pos1, sizeof(double) * 2 * a.n1, hipMemcpyHostToDevice, g->stream));
   if (a.same) {
     d2 = d1;
   } else {
     GU_TRY(grow(g, B_P2, (size_t)2 * a.n2, &d2));
-    if (a.n2) GU_HIP(hipMemcpyAsync(d2, pos2, sizeof(double) * 2 * a.n2, hipMemcpyHostToDevice, g->stream));
+    if (a.n2) GF_HIP(hipMemcpyAsync(d2, pos2, sizeof(double) * 2 * a.n2, hipMemcpyHostToDevice, g->stream));
   }
   a.p1 = d1;
   a.p2 = d2;
@@ -326,9 +316,9 @@ int finish(gu_graph* g, int64_t* n_edges, Fill launch_fill) {
   int64_t total = 0;
   if (a.n1 > 0) {
     gu_scan_kernel<<<1, 1024, 0, g->stream>>>(a);
-    GU_HIP(hipGetLastError());
-    GU_HIP(hipMemcpyAsync(&total, a.total, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    GU_HIP(hipStreamSynchronize(g->stream));
+    GF_HIP(hipGetLastError());
+    GF_HIP(hipMemcpyAsync(&total, a.total, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    GF_HIP(hipStreamSynchronize(g->stream));
   }
   GU_TRY(grow(g, B_SND, (size_t)total, &a.snd));
   GU_TRY(grow(g, B_RCV, (size_t)total, &a.rcv));
@@ -337,7 +327,7 @@ int finish(gu_graph* g, int64_t* n_edges, Fill launch_fill) {
   GU_TRY(grow(g, B_DY, (size_t)total, &a.dy));
   if (total > 0) {
     launch_fill();
-    GU_HIP(hipGetLastError());
+    GF_HIP(hipGetLastError());
   }
   g->n_edges = total;
   if (n_edges) *n_edges = total;
@@ -349,17 +339,14 @@ int finish(gu_graph* g, int64_t* n_edges, Fill launch_fill) {
 extern "C" {
 
 int gu_create(int device, gu_graph** out) {
-  if (!out) return gfail(GF_EINVAL, "null output pointer");
+  if (!out) return fail(GF_EINVAL, "null output pointer");
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return gfail(GF_EHIP, "no HIP device");
-  if (device < 0 || device >= ndev) return gfail(GF_EINVAL, "device out of range");
-  GU_HIP(hipSetDevice(device));
+  if (int rc = gf::select_device(device)) return rc;
   gu_graph* g = new gu_graph();
   g->device = device;
   if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
     delete g;
-    return gfail(GF_EHIP, "hipStreamCreate");
+    return fail(GF_EHIP, "hipStreamCreate");
   }
   *out = g;
   return GF_OK;
@@ -384,26 +371,26 @@ int gu_radius_edges(gu_graph* g, const double* pos1, int32_t n1, const double* p
   a.self_loops = self_loops != 0;
   if (a.n1 > 0) {
     gu_radius_count_kernel<<<row_grid(a.n1), kGuThreads, 0, g->stream>>>(a);
-    GU_HIP(hipGetLastError());
+    GF_HIP(hipGetLastError());
   }
   return finish(g, n_edges, [&] { gu_radius_fill_kernel<<<row_grid(a.n1), kGuThreads, 0, g->stream>>>(a); });
 }
 
 int gu_k_edges(gu_graph* g, int32_t k, const double* pos1, int32_t n1, const double* pos2, int32_t n2,
                int self_loops, int allow_nearest, int64_t* n_edges) {
-  if (k < 1) return gfail(GF_EINVAL, "k must be >= 1");
+  if (k < 1) return fail(GF_EINVAL, "k must be >= 1");
   GU_TRY(stage(g, pos1, n1, pos2, n2));
   GuArgs& a = g->a;
   // np.argpartition(r, kth) needs kth < the row length (kth = k - 1 or k)
   const int kth = allow_nearest ? k - 1 : k;
-  if (kth >= a.n2) return gfail(GF_EINVAL, "kth(=" + std::to_string(kth) + ") out of bounds (" + std::to_string(a.n2) + ")");
+  if (kth >= a.n2) return fail(GF_EINVAL, "kth(=" + std::to_string(kth) + ") out of bounds (" + std::to_string(a.n2) + ")");
   a.k = k;
   a.allow_nearest = allow_nearest != 0;
   a.self_loops = self_loops != 0;
   GU_TRY(grow(g, B_SEL, (size_t)a.n1 * (k + 1), &a.sel));
   if (a.n1 > 0) {
     gu_knn_select_kernel<<<row_grid(a.n1), kGuThreads, 0, g->stream>>>(a);
-    GU_HIP(hipGetLastError());
+    GF_HIP(hipGetLastError());
   }
   return finish(g, n_edges, [&] {
     gu_knn_fill_kernel<<<(a.n1 + kGuThreads - 1) / kGuThreads, kGuThreads, 0, g->stream>>>(a);
@@ -411,36 +398,36 @@ int gu_k_edges(gu_graph* g, int32_t k, const double* pos1, int32_t n1, const dou
 }
 
 int gu_get_edges(gu_graph* g, int32_t* senders, int32_t* receivers, double* r, double* diff) {
-  if (!g) return gfail(GF_EINVAL, "null graph context");
+  if (!g) return fail(GF_EINVAL, "null graph context");
   const int64_t E = g->n_edges;
-  GU_HIP(hipSetDevice(g->device));
+  GF_HIP(hipSetDevice(g->device));
   if (E > 0) {
     const GuArgs& a = g->a;
-    if (senders) GU_HIP(hipMemcpyAsync(senders, a.snd, sizeof(int32_t) * E, hipMemcpyDeviceToHost, g->stream));
-    if (receivers) GU_HIP(hipMemcpyAsync(receivers, a.rcv, sizeof(int32_t) * E, hipMemcpyDeviceToHost, g->stream));
-    if (r) GU_HIP(hipMemcpyAsync(r, a.r, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
+    if (senders) GF_HIP(hipMemcpyAsync(senders, a.snd, sizeof(int32_t) * E, hipMemcpyDeviceToHost, g->stream));
+    if (receivers) GF_HIP(hipMemcpyAsync(receivers, a.rcv, sizeof(int32_t) * E, hipMemcpyDeviceToHost, g->stream));
+    if (r) GF_HIP(hipMemcpyAsync(r, a.r, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
     if (diff) {
-      GU_HIP(hipMemcpyAsync(diff, a.dx, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
-      GU_HIP(hipMemcpyAsync(diff + E, a.dy, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
+      GF_HIP(hipMemcpyAsync(diff, a.dx, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
+      GF_HIP(hipMemcpyAsync(diff + E, a.dy, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
     }
   }
-  GU_HIP(hipStreamSynchronize(g->stream));
+  GF_HIP(hipStreamSynchronize(g->stream));
   return GF_OK;
 }
 
 int gu_nodes_within_radius(gu_graph* g, const double* pos1, int32_t n1, const double* pos2, int32_t n2, double rad,
                            uint8_t* valid) {
-  if (!pos2 || !valid) return gfail(GF_EINVAL, "pos2 and valid are required");
+  if (!pos2 || !valid) return fail(GF_EINVAL, "pos2 and valid are required");
   GU_TRY(stage(g, pos1, n1, pos2, n2));
   GuArgs& a = g->a;
   a.rad = rad;
   GU_TRY(grow(g, B_VALID, (size_t)a.n2, &a.valid));
   if (a.n2 > 0) {
     gu_within_kernel<<<(a.n2 + kGuThreads - 1) / kGuThreads, kGuThreads, 0, g->stream>>>(a);
-    GU_HIP(hipGetLastError());
-    GU_HIP(hipMemcpyAsync(valid, a.valid, a.n2, hipMemcpyDeviceToHost, g->stream));
+    GF_HIP(hipGetLastError());
+    GF_HIP(hipMemcpyAsync(valid, a.valid, a.n2, hipMemcpyDeviceToHost, g->stream));
   }
-  GU_HIP(hipStreamSynchronize(g->stream));
+  GF_HIP(hipStreamSynchronize(g->stream));
   return GF_OK;
 }
 

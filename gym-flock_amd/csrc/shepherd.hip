@@ -26,11 +26,10 @@
 #include <cstdint>
 #include <string>
 
-#include "gymflock.h"
+#include "capi_common.h"
 
-namespace gf {
-int set_error(int code, const std::string& msg);
-}
+using gf::dalloc;
+using gf::fail;
 
 namespace {
 
@@ -234,14 +233,6 @@ __global__ __launch_bounds__(256) void shep_cast_kernel(const double* src, float
   for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) dst[k] = (float)src[k];
 }
 
-int sfail(int code, const std::string& m) { return gf::set_error(code, m); }
-
-#define SH_HIP(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) return sfail(GF_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 }  // namespace
 
 struct shep_handle {
@@ -259,20 +250,6 @@ struct shep_handle {
 
 namespace {
 
-int use(shep_handle* h) {
-  SH_HIP(hipSetDevice(h->cfg.device));
-  return GF_OK;
-}
-
-template <class T>
-int alloc(T** p, size_t n) {
-  if (hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)) != hipSuccess) {
-    (void)hipGetLastError();
-    return sfail(GF_ENOMEM, "hipMalloc (shepherding)");
-  }
-  return GF_OK;
-}
-
 int launch(shep_handle* h, int mode, int n_steps, double* rew_steps) {
   ShepArgs a = h->a;
   a.mode = mode;
@@ -284,7 +261,7 @@ int launch(shep_handle* h, int mode, int n_steps, double* rew_steps) {
   } else {
     shep_kernel<false><<<(unsigned)a.B, (unsigned)((a.N + 63) / 64 * 64), 0, h->stream>>>(a);
   }
-  SH_HIP(hipGetLastError());
+  GF_HIP(hipGetLastError());
   return GF_OK;
 }
 
@@ -292,27 +269,27 @@ int launch(shep_handle* h, int mode, int n_steps, double* rew_steps) {
 int copy_out(shep_handle* h, const double* src, size_t n, void* dst, int flags) {
   const bool dev = flags & SHEP_OUT_DEVICE, f32 = flags & SHEP_OUT_F32;
   if (!f32) {
-    SH_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+    GF_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                           h->stream));
   } else {
     float* out = static_cast<float*>(dst);
     if (!dev) {
       if (h->scratch_cap < n * sizeof(float)) {
-        SH_HIP(hipStreamSynchronize(h->stream));
-        if (h->scratch) SH_HIP(hipFree(h->scratch));
+        GF_HIP(hipStreamSynchronize(h->stream));
+        if (h->scratch) GF_HIP(hipFree(h->scratch));
         h->scratch = nullptr;
         h->scratch_cap = 0;
-        if (int rc = alloc(reinterpret_cast<unsigned char**>(&h->scratch), n * sizeof(float))) return rc;
+        if (int rc = dalloc(reinterpret_cast<unsigned char**>(&h->scratch), n * sizeof(float))) return rc;
         h->scratch_cap = n * sizeof(float);
       }
       out = static_cast<float*>(h->scratch);
     }
     const unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     shep_cast_kernel<<<grid, 256, 0, h->stream>>>(src, out, n);
-    SH_HIP(hipGetLastError());
-    if (!dev) SH_HIP(hipMemcpyAsync(dst, out, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    GF_HIP(hipGetLastError());
+    if (!dev) GF_HIP(hipMemcpyAsync(dst, out, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   }
-  if (!dev) SH_HIP(hipStreamSynchronize(h->stream));  // device destinations: stream-ordered, shep_sync
+  if (!dev) GF_HIP(hipStreamSynchronize(h->stream));  // device destinations: stream-ordered, shep_sync
   return GF_OK;
 }
 
@@ -321,20 +298,17 @@ int copy_out(shep_handle* h, const double* src, size_t n, void* dst, int flags) 
 extern "C" {
 
 int shep_create(const shep_config* cfg, shep_handle** out) {
-  if (!cfg || !out) return sfail(GF_EINVAL, "null argument");
+  if (!cfg || !out) return fail(GF_EINVAL, "null argument");
   *out = nullptr;
-  if (cfg->n_shepherds < 1) return sfail(GF_EINVAL, "n_shepherds must be >= 1");
-  if (cfg->n_sheep < 1) return sfail(GF_EINVAL, "n_sheep must be >= 1");
+  if (cfg->n_shepherds < 1) return fail(GF_EINVAL, "n_shepherds must be >= 1");
+  if (cfg->n_sheep < 1) return fail(GF_EINVAL, "n_sheep must be >= 1");
   if ((int64_t)cfg->n_shepherds + cfg->n_sheep > kMaxAgents)
-    return sfail(GF_EINVAL, "n_shepherds + n_sheep must be <= 1024");
-  if (cfg->n_envs < 1) return sfail(GF_EINVAL, "n_envs must be >= 1");
-  if (!(cfg->dt > 0)) return sfail(GF_EINVAL, "dt must be > 0");
-  if (!(cfg->comm_radius > 0)) return sfail(GF_EINVAL, "comm_radius must be > 0");
-  if (!(cfg->goal_region_radius > 0)) return sfail(GF_EINVAL, "goal_region_radius must be > 0");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sfail(GF_EHIP, "no HIP device");
-  if (cfg->device < 0 || cfg->device >= ndev) return sfail(GF_EINVAL, "device out of range");
-  SH_HIP(hipSetDevice(cfg->device));
+    return fail(GF_EINVAL, "n_shepherds + n_sheep must be <= 1024");
+  if (cfg->n_envs < 1) return fail(GF_EINVAL, "n_envs must be >= 1");
+  if (!(cfg->dt > 0)) return fail(GF_EINVAL, "dt must be > 0");
+  if (!(cfg->comm_radius > 0)) return fail(GF_EINVAL, "comm_radius must be > 0");
+  if (!(cfg->goal_region_radius > 0)) return fail(GF_EINVAL, "goal_region_radius must be > 0");
+  if (int rc = gf::select_device(cfg->device)) return rc;
   shep_handle* h = new shep_handle();
   h->cfg = *cfg;
   ShepArgs& a = h->a;
@@ -351,16 +325,16 @@ int shep_create(const shep_config* cfg, shep_handle** out) {
   a.los5 = 5.0 * (M_PI / 180.0);
   const size_t BN = (size_t)a.B * a.N;
   int rc = GF_OK;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) rc = sfail(GF_EHIP, "hipStreamCreate");
-  if (!rc) rc = alloc(&a.x, BN * 3);
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(GF_EHIP, "hipStreamCreate");
+  if (!rc) rc = dalloc(&a.x, BN * 3);
   // observation, adjacency and rewards in one block: shep_get_outputs is one copy
-  if (!rc) rc = alloc(&a.obs, BN * 4 + BN * a.N + (size_t)a.B);
+  if (!rc) rc = dalloc(&a.obs, BN * 4 + BN * a.N + (size_t)a.B);
   if (!rc) {
     a.adj = a.obs + BN * 4;
     a.rew = a.adj + BN * a.N;
   }
-  if (!rc) rc = alloc(&a.ctrl, BN * 2);
-  if (!rc) rc = alloc(&h->ubuf, (size_t)a.B * a.nsh * 2);
+  if (!rc) rc = dalloc(&a.ctrl, BN * 2);
+  if (!rc) rc = dalloc(&h->ubuf, (size_t)a.B * a.nsh * 2);
   if (rc) {
     shep_destroy(h);
     return rc;
@@ -383,54 +357,54 @@ int shep_destroy(shep_handle* h) {
 }
 
 int shep_set_state(shep_handle* h, const double* x) {
-  if (!h || !x) return sfail(GF_EINVAL, "null argument");
-  if (int rc = use(h)) return rc;
-  SH_HIP(hipMemcpyAsync(h->a.x, x, sizeof(double) * 3 * h->a.B * h->a.N, hipMemcpyHostToDevice, h->stream));
-  SH_HIP(hipStreamSynchronize(h->stream));
+  if (!h || !x) return fail(GF_EINVAL, "null argument");
+  GF_HIP(hipSetDevice(h->cfg.device));
+  GF_HIP(hipMemcpyAsync(h->a.x, x, sizeof(double) * 3 * h->a.B * h->a.N, hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   h->has_state = true;
   h->has_obs = h->has_ctrl = false;
   return GF_OK;
 }
 
 int shep_get_state(shep_handle* h, double* x) {
-  if (!h || !x) return sfail(GF_EINVAL, "null argument");
-  if (!h->has_state) return sfail(GF_ESTATE, "set a state first (shep_set_state)");
-  if (int rc = use(h)) return rc;
-  SH_HIP(hipMemcpyAsync(x, h->a.x, sizeof(double) * 3 * h->a.B * h->a.N, hipMemcpyDeviceToHost, h->stream));
-  SH_HIP(hipStreamSynchronize(h->stream));
+  if (!h || !x) return fail(GF_EINVAL, "null argument");
+  if (!h->has_state) return fail(GF_ESTATE, "set a state first (shep_set_state)");
+  GF_HIP(hipSetDevice(h->cfg.device));
+  GF_HIP(hipMemcpyAsync(x, h->a.x, sizeof(double) * 3 * h->a.B * h->a.N, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
 int shep_observe(shep_handle* h) {
-  if (!h) return sfail(GF_EINVAL, "null handle");
-  if (!h->has_state) return sfail(GF_ESTATE, "set a state first (shep_set_state)");
-  if (int rc = use(h)) return rc;
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_state) return fail(GF_ESTATE, "set a state first (shep_set_state)");
+  GF_HIP(hipSetDevice(h->cfg.device));
   if (int rc = launch(h, M_OBSERVE, 0, nullptr)) return rc;
   h->has_obs = true;
   return GF_OK;
 }
 
 int shep_step(shep_handle* h, const void* u, int flags) {
-  if (!h) return sfail(GF_EINVAL, "null handle");
-  if (flags & ~(SHEP_U_DEVICE | SHEP_U_F64 | SHEP_U_EXPERT | SHEP_U_RESIDENT)) return sfail(GF_EINVAL, "unknown flag");
-  if (!h->has_state) return sfail(GF_ESTATE, "set a state first (shep_set_state)");
-  if (int rc = use(h)) return rc;
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (flags & ~(SHEP_U_DEVICE | SHEP_U_F64 | SHEP_U_EXPERT | SHEP_U_RESIDENT)) return fail(GF_EINVAL, "unknown flag");
+  if (!h->has_state) return fail(GF_ESTATE, "set a state first (shep_set_state)");
+  GF_HIP(hipSetDevice(h->cfg.device));
   ShepArgs& a = h->a;
   int mode = M_STEP;
   if (flags & SHEP_U_EXPERT) {
     mode = M_ROLLOUT;
   } else if (flags & SHEP_U_RESIDENT) {
-    if (!h->has_u) return sfail(GF_ESTATE, "no resident actions (a host-action shep_step or shep_controller first)");
+    if (!h->has_u) return fail(GF_ESTATE, "no resident actions (a host-action shep_step or shep_controller first)");
     a.u = h->ubuf;
     a.u_f64 = h->u_f64;
   } else {
-    if (!u) return sfail(GF_EINVAL, "null actions");
+    if (!u) return fail(GF_EINVAL, "null actions");
     const int f64 = (flags & SHEP_U_F64) ? 1 : 0;
     if (flags & SHEP_U_DEVICE) {
       a.u = u;
     } else {
       // pageable host memory: the copy has left the caller's buffer when this returns
-      SH_HIP(hipMemcpyAsync(h->ubuf, u, (size_t)a.B * a.nsh * 2 * (f64 ? 8 : 4), hipMemcpyHostToDevice, h->stream));
+      GF_HIP(hipMemcpyAsync(h->ubuf, u, (size_t)a.B * a.nsh * 2 * (f64 ? 8 : 4), hipMemcpyHostToDevice, h->stream));
       a.u = h->ubuf;
       h->has_u = true;
       h->u_f64 = f64;
@@ -443,48 +417,48 @@ int shep_step(shep_handle* h, const void* u, int flags) {
 }
 
 int shep_controller(shep_handle* h, double* out) {
-  if (!h) return sfail(GF_EINVAL, "null handle");
-  if (!h->has_state) return sfail(GF_ESTATE, "set a state first (shep_set_state)");
-  if (int rc = use(h)) return rc;
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_state) return fail(GF_ESTATE, "set a state first (shep_set_state)");
+  GF_HIP(hipSetDevice(h->cfg.device));
   if (int rc = launch(h, M_CONTROLLER, 1, nullptr)) return rc;
   h->has_u = true;  // the output is the resident action buffer, float64
   h->u_f64 = 1;
   if (out) {
-    SH_HIP(hipMemcpyAsync(out, h->ubuf, sizeof(double) * 2 * h->a.B * h->a.nsh, hipMemcpyDeviceToHost, h->stream));
-    SH_HIP(hipStreamSynchronize(h->stream));
+    GF_HIP(hipMemcpyAsync(out, h->ubuf, sizeof(double) * 2 * h->a.B * h->a.nsh, hipMemcpyDeviceToHost, h->stream));
+    GF_HIP(hipStreamSynchronize(h->stream));
   }
   return GF_OK;
 }
 
 int shep_step_expert(shep_handle* h, int n_steps, double* rewards) {
-  if (!h) return sfail(GF_EINVAL, "null handle");
-  if (n_steps < 1) return sfail(GF_EINVAL, "n_steps must be >= 1");
-  if (!h->has_state) return sfail(GF_ESTATE, "set a state first (shep_set_state)");
-  if (int rc = use(h)) return rc;
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (n_steps < 1) return fail(GF_EINVAL, "n_steps must be >= 1");
+  if (!h->has_state) return fail(GF_ESTATE, "set a state first (shep_set_state)");
+  GF_HIP(hipSetDevice(h->cfg.device));
   const size_t n = (size_t)n_steps * h->a.B;
   if (h->rew_steps_cap < n) {
-    SH_HIP(hipStreamSynchronize(h->stream));
-    if (h->rew_steps) SH_HIP(hipFree(h->rew_steps));
+    GF_HIP(hipStreamSynchronize(h->stream));
+    if (h->rew_steps) GF_HIP(hipFree(h->rew_steps));
     h->rew_steps = nullptr;
     h->rew_steps_cap = 0;
-    if (int rc = alloc(&h->rew_steps, n)) return rc;
+    if (int rc = dalloc(&h->rew_steps, n)) return rc;
     h->rew_steps_cap = n;
   }
   if (int rc = launch(h, M_ROLLOUT, n_steps, h->rew_steps)) return rc;
   h->has_obs = h->has_ctrl = true;
   if (rewards) {
-    SH_HIP(hipMemcpyAsync(rewards, h->rew_steps, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-    SH_HIP(hipStreamSynchronize(h->stream));
+    GF_HIP(hipMemcpyAsync(rewards, h->rew_steps, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    GF_HIP(hipStreamSynchronize(h->stream));
   }
   return GF_OK;
 }
 
 // per_env doubles of every env from one of the observation buffers
 static int get_out(shep_handle* h, double* const ShepArgs::*buf, size_t per_env, void* dst, int flags) {
-  if (!h || !dst) return sfail(GF_EINVAL, "null argument");
-  if (flags & ~(SHEP_OUT_DEVICE | SHEP_OUT_F32)) return sfail(GF_EINVAL, "unknown flag");
-  if (!h->has_obs) return sfail(GF_ESTATE, "no observation yet (shep_observe or shep_step first)");
-  if (int rc = use(h)) return rc;
+  if (!h || !dst) return fail(GF_EINVAL, "null argument");
+  if (flags & ~(SHEP_OUT_DEVICE | SHEP_OUT_F32)) return fail(GF_EINVAL, "unknown flag");
+  if (!h->has_obs) return fail(GF_ESTATE, "no observation yet (shep_observe or shep_step first)");
+  GF_HIP(hipSetDevice(h->cfg.device));
   return copy_out(h, h->a.*buf, (size_t)h->a.B * per_env, dst, flags);
 }
 
@@ -503,16 +477,16 @@ int shep_get_outputs(shep_handle* h, double* dst) {
 }
 
 int shep_get_controls(shep_handle* h, double* dst) {
-  if (!h || !dst) return sfail(GF_EINVAL, "null argument");
-  if (!h->has_ctrl) return sfail(GF_ESTATE, "no step yet (shep_step or shep_step_expert first)");
-  if (int rc = use(h)) return rc;
+  if (!h || !dst) return fail(GF_EINVAL, "null argument");
+  if (!h->has_ctrl) return fail(GF_ESTATE, "no step yet (shep_step or shep_step_expert first)");
+  GF_HIP(hipSetDevice(h->cfg.device));
   return copy_out(h, h->a.ctrl, (size_t)h->a.B * h->a.N * 2, dst, 0);
 }
 
 int shep_sync(shep_handle* h) {
-  if (!h) return sfail(GF_EINVAL, "null handle");
-  if (int rc = use(h)) return rc;
-  SH_HIP(hipStreamSynchronize(h->stream));
+  if (!h) return fail(GF_EINVAL, "null handle");
+  GF_HIP(hipSetDevice(h->cfg.device));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 

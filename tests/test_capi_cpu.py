@@ -16,7 +16,7 @@ HEADER = os.path.join(ROOT, "include", "gymflock.h")
 
 def declared_symbols():
     txt = open(HEADER).read()
-    return sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+((?:fe|cov|gu)_\w+)\s*\(", txt, re.M)))
+    return sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+((?:fe|cov|gu|shep)_\w+)\s*\(", txt, re.M)))
 
 
 def test_header_declares_the_abi():

@@ -4,13 +4,12 @@ the shepherd controller, the package's registration of the env and the shep_* C-
 import ctypes
 import inspect
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import shepherding_numpy as sn  # noqa: E402
@@ -126,15 +125,11 @@ def test_vec_reset_draws_the_recorded_initial_state():
         assert np.all(f["x"][0][:, 2] == 0)
 
 
-def shep_symbols():
-    txt = open(os.path.join(ROOT, "include", "gymflock.h")).read()
-    return sorted(set(re.findall(r"^\s*int\s+(shep_\w+)\s*\(", txt, re.M)))
-
-
 def test_every_declared_shep_symbol_is_exported_and_bound():
     from gym_flock import _native as nat
+    from test_capi_cpu import declared_symbols  # the one parser of include/gymflock.h
     lib = nat.load()
-    syms = shep_symbols()
+    syms = [s for s in declared_symbols() if s.startswith("shep_")]
     for s in ("shep_create", "shep_destroy", "shep_set_state", "shep_get_state", "shep_observe", "shep_step",
               "shep_controller", "shep_step_expert", "shep_get_obs", "shep_get_adj", "shep_get_rewards", "shep_sync"):
         assert s in syms
