@@ -143,7 +143,7 @@ void release(fe_handle* h) {
   comm_release(h, false);
   void* bufs[] = {h->x[0], h->x[1], h->u, h->ctrl[0], h->ctrl[1], h->sv, h->net, h->reward_ring,
                   h->knn_idx[0], h->knn_idx[1], h->knn_obs[0], h->knn_obs[1], h->knn_r2[0], h->knn_r2[1], h->knn_rimflag[0], h->knn_rimflag[1], h->vel_diffs, h->min_dists, h->degree, h->stats_sum, h->dt_env,
-                  h->adj_bits[0], h->adj_bits[1], h->pdeg[0], h->pdeg[1]};
+                  h->adj_bits[0], h->adj_bits[1], h->pdeg[0], h->pdeg[1], h->net_bits, h->net_val};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->fin_cnt) hipFree(h->fin_cnt);
@@ -292,6 +292,10 @@ gf::StepArgs env_range(const fe_handle* h, const gf::StepArgs& a, int b0, int nb
   if (a.u) r.u = static_cast<const char*>(a.u) + e0 * 2 * (uf64 ? 8 : 4);
   if (a.state_values) r.state_values = a.state_values + e0 * 6;
   if (a.network) r.network = a.network + e0 * N;
+  if (a.net_bits) {
+    r.net_bits = a.net_bits + e0 * Wn;
+    r.net_val = a.net_val + e0;
+  }
   if (a.ctrl_out) r.ctrl_out = a.ctrl_out + e0 * 2;
   if (a.reward) r.reward = a.reward + b0;
   if (a.reward2) r.reward2 = a.reward2 + b0;
@@ -308,7 +312,53 @@ gf::StepArgs env_range(const fe_handle* h, const gf::StepArgs& a, int b0, int nb
   return r;
 }
 
+// How a step launch stores the network: the one place that decides ("Delta
+// network store"), from the launch's own arguments and the handle's net_record_valid.
+//   eligible, record valid                        delta    record stays valid
+//   eligible, record not valid                    force    record valid afterwards
+//   not eligible, writes the handle's buffer      full     record not valid afterwards
+//   no network, or one sent to mapped host memory: the buffer and the record stay as they are
+// Eligible: the plain step family (no controller, variant, fused kNN or inline actions)
+// with N % 4 == 0 and FE_NET_DELTA. Every launch of a step (split, de-phased, single)
+// gets the step's mode: each env's rows are written by one launch per step, and the
+// launches of consecutive steps that write the same env are ordered by their streams.
+int net_store_mode(fe_handle* h, gf::StepArgs& a, bool ctrl) {
+  a.net_bits = nullptr;
+  a.net_val = nullptr;
+  a.net_force = 0;
+  if (!a.network || a.network != h->net) return GF_OK;
+  const bool eligible = h->net_store == FE_NET_DELTA && !ctrl && !a.variant && !a.knn_idx && !a.u_inline &&
+                        (a.N & 3) == 0 && !a.diag;
+  if (!eligible) {
+    h->net_record_valid = false;
+    return GF_OK;
+  }
+  if (!h->net_bits || !h->net_val) {
+    h->net_record_valid = false;
+    if (!h->net_bits)
+      if (int rc = dalloc(&h->net_bits, h->BN * ((h->cfg.n_agents + 63) / 64))) return rc;
+    if (!h->net_val)
+      if (int rc = dalloc(&h->net_val, h->BN)) return rc;
+  }
+  a.net_bits = h->net_bits;
+  a.net_val = h->net_val;
+  a.net_force = h->net_record_valid ? 0 : 1;
+  h->net_record_valid = true;
+  return GF_OK;
+}
+
+int timed_launch_mode(fe_handle* h, const gf::StepArgs& a, bool dyn, bool uf64, bool ctrl);
+
 int timed_launch(fe_handle* h, const gf::StepArgs& a_in, bool dyn, bool uf64, bool ctrl) {
+  gf::StepArgs a = a_in;
+  if (int rc = net_store_mode(h, a, ctrl)) return rc;
+  const int rc = timed_launch_mode(h, a, dyn, uf64, ctrl);
+  // a launch that failed may have stored some of a step's rows and not others
+  if (rc != GF_OK && a.network == h->net) h->net_record_valid = false;
+  return rc;
+}
+
+int timed_launch_mode(fe_handle* h, const gf::StepArgs& a_in, bool dyn, bool uf64, bool ctrl) {
   gf::StepArgs a = a_in;
   a.store_fast = h->store_fast[ctrl ? 1 : 0];
   const bool split = split_next(h, a.B);
@@ -1360,6 +1410,18 @@ int fe_device_buffers(fe_handle* h, fe_buffers* out) {
   return GF_OK;
 }
 
+int fe_set_network_store(fe_handle* h, int mode) {
+  if (!h || (mode != FE_NET_DELTA && mode != FE_NET_FULL)) return fail(GF_EINVAL, "mode must be FE_NET_DELTA or FE_NET_FULL");
+  h->net_store = mode;  // read by the next launch (net_store_mode): a full store drops the record
+  return GF_OK;
+}
+
+int fe_network_touched(fe_handle* h) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  h->net_record_valid = false;
+  return GF_OK;
+}
+
 int fe_sync(fe_handle* h) {
   if (!h) return fail(GF_EINVAL, "null handle");
   if (int rc = use_dev(h)) return rc;
@@ -1450,6 +1512,7 @@ int fe_diag(fe_handle* h, int what, int reps, double* avg_ms) {
   GF_HIP(hipEventCreate(&e0));
   GF_HIP(hipEventCreate(&e1));
   const size_t bytes = h->BN * (size_t)h->cfg.n_agents * 4;
+  h->net_record_valid = false;  // the fill overwrites the network buffer
   GF_HIP(hipEventRecord(e0, h->stream));
   for (int r = 0; r < reps; ++r) {
     hipError_t e = gf::launch_fill(h->net, bytes, what == 1, h->stream);

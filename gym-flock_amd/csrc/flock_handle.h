@@ -44,6 +44,15 @@ struct fe_handle {
   int ccur = 0;
   float* sv = nullptr;
   float* net = nullptr;
+  // Delta network store (timed_launch): the record of what `net` holds, allocated on first
+  // use. Row i of the buffer holds net_val[i] at the set bits of net_bits[i] and +0.0f
+  // elsewhere: a description of the buffer, not of the state, so whatever leaves the
+  // buffer alone (FE_NO_NETWORK, set_state, reset, set_params, a network sent to
+  // page-locked host memory) leaves the record valid.
+  uint64_t* net_bits = nullptr;         // (B,N,ceil(N/64))
+  float* net_val = nullptr;             // (B,N)
+  bool net_record_valid = false;        // the record describes the buffer (host flag)
+  int net_store = FE_NET_DELTA;         // fe_set_network_store
   double* reward_ring = nullptr;        // kRewardSlots x B
   int rslot = 0;
   int64_t steps_written = 0;            // reward-writing launches so far (slot = count % slots)

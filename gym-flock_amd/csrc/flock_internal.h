@@ -28,6 +28,8 @@ constexpr int kKnnLdsMax = 4096;    // kNN stages the env's positions in LDS up 
 constexpr int kKnnGridCells = 2048; // kNN: cells of the per-env uniform grid (at most)
 constexpr int kInlineRimU = 4;      // fused kNN inline rim scan: columns in flight per lane
 constexpr int kStoreTab = 16;      // network rows: float4 table entries per wave (one per nibble)
+constexpr int kNetDeltaBatch = 64;  // delta network store: record words a wave compares at a time
+constexpr size_t kNetDeltaLds = 4 * kNetDeltaBatch * 8;  // their changed bits in LDS, per wave
 constexpr int kStepInlineRim = 2;  // fused kNN: unranked rows a wave ranks itself (more: rim kernel)
 constexpr int kStepExactKnnMax = 128;  // fused kNN: envs up to this size are ranked exactly in
                                        // the step (KX: one tile in LDS, no rim kernel)
@@ -102,6 +104,13 @@ struct StepArgs {
   int knn_jbits;          // bits of the agent index (qbits = 32 - jbits)
   int knn_exact;          // the handle's fused selection is exact in the step (step_knn_exact)
   DoneFlag fin;           // drop-in launch: the grid's completion flag (done_flag.h)
+  // Delta network store (the plain step into the handle's own buffer, N % 4 == 0; set by
+  // the C-ABI's timed_launch only): the record of what `network` holds. Row i holds
+  // net_val[i] at the set bits of net_bits[i] and +0.0f elsewhere; the launch stores only
+  // the groups (net_delta.h) whose content changes and brings the record up to date.
+  uint64_t* net_bits;     // (B,N,Wn) or nullptr: every row stored in full, no record kept
+  float* net_val;         // (B,N)
+  int net_force;          // store every group and write the record (its content is not valid)
 };
 
 // The drop-in step's actions passed in the kernel arguments (fe_step_host, one env of up

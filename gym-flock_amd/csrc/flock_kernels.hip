@@ -20,6 +20,7 @@
 // reference's bit pattern (dx*dx + dy*dy, two roundings then a sum); adjacency is
 // therefore bit-exact, and features differ from NumPy only by summation order.
 #include "flock_internal.h"
+#include "net_delta.h"
 
 #include <float.h>
 #include <limits.h>
@@ -694,6 +695,121 @@ __device__ __forceinline__ void store_network_rows(const StepArgs& a, const uint
   }
 }
 
+// Delta form of the vec4 loop above, for the plain step into the handle's own buffer
+// (N % 4 == 0, StepArgs.net_bits): only the groups of kNetGroupBytes whose content changes
+// are stored (net_delta.h), against the record of what the buffer holds. A wave's rows
+// [r0, r0 + nr) are one contiguous range of record words, compared kNetDeltaBatch at a
+// time: whole rows per batch while a row has at most that many words, 64-word chunks of
+// one row beyond. Lane l holds word l of a batch; the batches' recorded words are loaded
+// two ahead (the first two before the degrees are summed), so their round trip is off the
+// store loop. The batch's changed bits (recorded ^ new) go to the wave's own LDS words,
+// from which every lane takes those of its float4's group.
+struct NetDelta {
+  int r0, nr;        // the wave's rows of the block
+  int cpr, rpb, nb;  // 64-word chunks per row, rows per batch (cpr == 1), batches
+  uint64_t o0, o1;   // recorded words of the next two batches
+  float ov;          // lane m: recorded value of the wave's row m
+};
+struct NetDeltaBatch {
+  int m0, nrb;  // first row (of the wave's) and rows
+  int wf, cnt;  // first word (of the wave's range) and words
+  int cw0;      // first word of the rows' columns in this batch
+};
+__device__ __forceinline__ NetDeltaBatch net_delta_batch(const NetDelta& d, int Wn, int b) {
+  NetDeltaBatch t;
+  if (d.cpr == 1) {
+    t.m0 = b * d.rpb;
+    t.nrb = min(d.rpb, d.nr - t.m0);
+    t.wf = t.m0 * Wn;
+    t.cnt = t.nrb * Wn;
+    t.cw0 = 0;
+  } else {
+    t.m0 = b / d.cpr;
+    t.nrb = 1;
+    t.cw0 = (b - t.m0 * d.cpr) * kNetDeltaBatch;
+    t.wf = t.m0 * Wn + t.cw0;
+    t.cnt = min(kNetDeltaBatch, Wn - t.cw0);
+  }
+  return t;
+}
+__device__ __forceinline__ uint64_t net_delta_load(const StepArgs& a, const NetDelta& d, int Wn, size_t grow0, int b,
+                                                   int lane) {
+  if (b >= d.nb || a.net_force) return 0ull;
+  const NetDeltaBatch t = net_delta_batch(d, Wn, b);
+  return lane < t.cnt ? a.net_bits[(grow0 + d.r0) * (size_t)Wn + t.wf + lane] : 0ull;
+}
+__device__ __forceinline__ NetDelta net_delta_begin(const StepArgs& a, int Wn, size_t grow0, int nrows, int wid,
+                                                    int lane) {
+  NetDelta d;
+  const int per = (nrows + 3) >> 2;  // the rows of a wave, as store_network_rows deals them
+  d.r0 = wid * per;
+  d.nr = max(0, min(per, nrows - d.r0));
+  d.cpr = (Wn + kNetDeltaBatch - 1) / kNetDeltaBatch;
+  d.rpb = d.cpr == 1 ? kNetDeltaBatch / Wn : 1;
+  d.nb = d.cpr == 1 ? (d.nr + d.rpb - 1) / d.rpb : d.nr * d.cpr;
+  d.o0 = net_delta_load(a, d, Wn, grow0, 0, lane);
+  d.o1 = net_delta_load(a, d, Wn, grow0, 1, lane);
+  d.ov = (lane < d.nr && !a.net_force) ? a.net_val[grow0 + d.r0 + lane] : 0.f;
+  return d;
+}
+__device__ __forceinline__ void store_network_rows_delta(const StepArgs& a, const uint64_t* adj, const float* inv,
+                                                         uint64_t* dfl, NetDelta& d, int Wn, size_t grow0, int lane) {
+  const int N = a.N, nq = N >> 2;
+  const bool force = a.net_force != 0;
+  const size_t gr0 = grow0 + d.r0;
+  // the rows' values: lane m compares (bit patterns) and records row m's
+  bool vch = false;
+  if (lane < d.nr) {
+    const float ivl = inv[d.r0 + lane];
+    vch = force || __float_as_uint(ivl) != __float_as_uint(d.ov);
+    if (vch) a.net_val[gr0 + lane] = ivl;
+  }
+  const uint64_t vmask = __ballot(vch);
+  const unsigned* adj32 = reinterpret_cast<const unsigned*>(adj);
+  const unsigned* fl32 = reinterpret_cast<const unsigned*>(dfl);
+  const int o0 = (lane & 7) << 2;  // this lane's float4: its nibble of a 32-bit word
+  for (int b = 0; b < d.nb; ++b) {
+    const uint64_t old = d.o0;
+    d.o0 = d.o1;
+    d.o1 = net_delta_load(a, d, Wn, grow0, b + 2, lane);
+    const NetDeltaBatch t = net_delta_batch(d, Wn, b);
+    if (lane < t.cnt) {
+      const uint64_t nw = adj[(size_t)d.r0 * Wn + t.wf + lane];
+      const uint64_t x = force ? ~0ull : (old ^ nw);
+      dfl[lane] = x;
+      if (x) a.net_bits[gr0 * (size_t)Wn + t.wf + lane] = nw;
+    }
+    // the wave's LDS operations run in order: the words above precede the reads below,
+    // which precede the next batch's words (the fences keep the compiler to that order)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int nqc = min(nq - (t.cw0 << 4), kNetDeltaBatch * 16);  // float4s of a row in this batch
+    for (int rr = 0; rr < t.nrb; ++rr) {
+      const int m = t.m0 + rr, r = d.r0 + m;
+      const bool vc = (vmask >> m) & 1ull;
+      const unsigned ivb = __float_as_uint(inv[r]);
+      f4v* r4 = reinterpret_cast<f4v*>(a.network + (grow0 + r) * (size_t)N) + (t.cw0 << 4);
+      const unsigned* nrow = adj32 + ((size_t)r * Wn + t.cw0) * 2;
+      const unsigned* frow = fl32 + (d.cpr == 1 ? rr * Wn * 2 : 0);
+      for (int q = lane; q < nqc; q += 64) {
+        const unsigned nw32 = nrow[q >> 3];
+        if (net_group_dirty<kNetGroupBytes>(net_delta_bits(frow[q >> 3], nw32, vc), o0)) {
+          // set bits take the row's value, clear ones +0.0f
+          const unsigned nib = nw32 >> o0;
+          f4v v;
+          v.x = __uint_as_float(ivb & (0u - (nib & 1u)));
+          v.y = __uint_as_float(ivb & (0u - ((nib >> 1) & 1u)));
+          v.z = __uint_as_float(ivb & (0u - ((nib >> 2) & 1u)));
+          v.w = __uint_as_float(ivb & (0u - ((nib >> 3) & 1u)));
+          r4[q] = v;
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 // Per-row outputs of a row block once its features are summed: the S slices of each
 // row combined, state_values (:124-129), the updated state, the controller (:194-226)
 // and, by the env's first block, the reward (instant_cost :145-147). `writer` = the
@@ -856,7 +972,10 @@ __device__ unsigned long long gf_stamp_buf[8192 * 16];
 // KX > 0 (Flocking-v0 in an env of one tile, N <= kStepExactKnnMax; KN == 0): after the
 // epilogue every row is ranked exactly against the whole env, staged in LDS as the tile
 // (below): no keys in the feature pass, no unranked rows, no rim kernel.
-template <bool DYN, bool UF64, bool CTRL, bool VAR, int PF = 0, int KN = 0, bool UIN = false, int KX = 0>
+// DN (the plain step only: no CTRL, VAR, KN, UIN, KX): the network rows go out in their
+// delta form (store_network_rows_delta), against the record in StepArgs.net_bits / net_val.
+template <bool DYN, bool UF64, bool CTRL, bool VAR, int PF = 0, int KN = 0, bool UIN = false, int KX = 0,
+          bool DN = false>
 __global__ __launch_bounds__(kThreads, VAR ? 1
                                            : (PF ? kWavesPf
                                                  : (KN ? (CTRL ? kWavesKnnCtrl : kWavesKnn)
@@ -1410,6 +1529,10 @@ void flock_step_kernel(typename std::conditional<UIN, StepArgsU, StepArgs>::type
   const int nchl = (N - jl + 63) >> 6;
   if constexpr (kSup) __syncthreads();  // the last feature pass's adjacency words
 
+  // DN: the record's first words are on their way while the degrees are summed
+  [[maybe_unused]] NetDelta nd;
+  if constexpr (DN) nd = net_delta_begin(a, Wn, env0 + i0, nrows, wid, lane);
+
   // degree of each row -> 1/deg for the mean-pooled network (:120-122)
   {
     int deg = 0;
@@ -1432,7 +1555,13 @@ void flock_step_kernel(typename std::conditional<UIN, StepArgsU, StepArgs>::type
   __syncthreads();
   GF_STAMP(7);
 
-  if (a.network) store_network_rows(a, adj, inv, stab, Wn, env0 + i0, nrows, wid, lane, KN > 0);
+  if constexpr (DN) {
+    // its LDS words follow the block's other arrays (step_lds_bytes)
+    uint64_t* dfl = reinterpret_cast<uint64_t*>(inv + ((R + 3) & ~3)) + wid * kNetDeltaBatch;
+    store_network_rows_delta(a, adj, inv, dfl, nd, Wn, env0 + i0, lane);
+  } else {
+    if (a.network) store_network_rows(a, adj, inv, stab, Wn, env0 + i0, nrows, wid, lane, KN > 0);
+  }
 
   GF_STAMP(8);
   if constexpr (!kSup) feature_pass(jl, nchl);
@@ -2006,20 +2135,21 @@ hipError_t max_lds_once(const void* f, std::atomic<uint64_t>& done, int bytes) {
   return e;
 }
 
-template <bool DYN, bool UF64, bool CTRL, bool VAR, int PF = 0, int KN = 0, int KX = 0>
+template <bool DYN, bool UF64, bool CTRL, bool VAR, int PF = 0, int KN = 0, int KX = 0, bool DN = false>
 static hipError_t launch_step_tiled(const StepArgs& a, hipStream_t s) {
-  size_t lds = step_lds_bytes(a.N, a.R, a.T, CTRL, KN > 0);
+  size_t lds = step_lds_bytes(a.N, a.R, a.T, CTRL, KN > 0) + (DN ? kNetDeltaLds : 0);
   // the plain step runs best at 6 workgroups per CU: 199 us vs 206 at the 7 its 21.2 KiB
   // would allow
   if (!CTRL && !VAR && lds < kStepLdsPlainFloor) lds = kStepLdsPlainFloor;
   static std::atomic<uint64_t> attr{0};
   if (const hipError_t e = max_lds_once(
-          reinterpret_cast<const void*>(&flock_step_kernel<DYN, UF64, CTRL, VAR, PF, KN, false, KX>), attr, 160 * 1024);
+          reinterpret_cast<const void*>(&flock_step_kernel<DYN, UF64, CTRL, VAR, PF, KN, false, KX, DN>), attr,
+          160 * 1024);
       e != hipSuccess)
     return e;
   const int grid = a.B * a.bpe;
-  hipLaunchKernelGGL((flock_step_kernel<DYN, UF64, CTRL, VAR, PF, KN, false, KX>), dim3(grid), dim3(kThreads), lds, s,
-                     a);
+  hipLaunchKernelGGL((flock_step_kernel<DYN, UF64, CTRL, VAR, PF, KN, false, KX, DN>), dim3(grid), dim3(kThreads), lds,
+                     s, a);
   return hipGetLastError();
 }
 
@@ -2055,6 +2185,7 @@ bool step_knn_exact(int N, int T, int B) {
 
 template <bool DYN, bool UF64, bool CTRL>
 static hipError_t launch_step_t(const StepArgs& a, hipStream_t s) {
+  if (a.net_bits && (a.u_inline || a.knn_idx)) return hipErrorInvalidValue;
   if constexpr (DYN) {
     const bool exact = a.knn_idx && a.knn_exact;
     if (a.u_inline) {
@@ -2075,8 +2206,17 @@ static hipError_t launch_step_t(const StepArgs& a, hipStream_t s) {
     }
   }
   if (a.knn_idx) return hipErrorInvalidValue;
-  if (a.variant) return launch_step_tiled<DYN, UF64, CTRL, true>(a, s);
-  if (a.prefetch && a.T <= 2 * kThreads && a.N > a.T) return launch_step_tiled<DYN, UF64, CTRL, false, 1>(a, s);
+  if (a.variant) return a.net_bits ? hipErrorInvalidValue : launch_step_tiled<DYN, UF64, CTRL, true>(a, s);
+  const bool pf = a.prefetch && a.T <= 2 * kThreads && a.N > a.T;
+  if (a.net_bits) {  // the delta network store: the plain step family only (timed_launch decides)
+    if constexpr (CTRL) return hipErrorInvalidValue;
+    else {
+      if (!a.network || !a.net_val || (a.N & 3) || a.diag) return hipErrorInvalidValue;
+      if (pf) return launch_step_tiled<DYN, UF64, false, false, 1, 0, 0, true>(a, s);
+      return launch_step_tiled<DYN, UF64, false, false, 0, 0, 0, true>(a, s);
+    }
+  }
+  if (pf) return launch_step_tiled<DYN, UF64, CTRL, false, 1>(a, s);
   return launch_step_tiled<DYN, UF64, CTRL, false>(a, s);
 }
 

@@ -27,6 +27,8 @@ FE_NO_NETWORK = 0x20
 FE_NO_STATE_VALUES = 0x40
 FE_U_RESIDENT = 0x80
 FE_PACKED_NETWORK = 0x100
+FE_NET_DELTA = 0
+FE_NET_FULL = 1
 FE_OUT_MAPPED = 0x1  # fe_get_outputs flag
 FE_RESET_SEED = 0x1  # fe_reset_device flags
 FE_RESET_NO_REJECT = 0x2
@@ -191,6 +193,8 @@ SIGNATURES = {
     "fe_host_free": [_P],
     "fe_get_knn": [_P, _I, _P, _P],
     "fe_device_buffers": [_P, ctypes.POINTER(FeBuffers)],
+    "fe_set_network_store": [_P, _I],
+    "fe_network_touched": [_P],
     "fe_sync": [_P],
     "fe_set_streams": [_P, _I],
     "fe_join": [_P],
@@ -494,6 +498,24 @@ class FlockHandle:
         h = ctypes.c_void_p()
         check(self.lib.fe_create(ctypes.byref(self.cfg), ctypes.byref(h)))
         self.h = h
+        # GYMFLOCK_NET_STORE=full|delta: how the plain step stores the dense network
+        # (fe_set_network_store; the library's default is delta), for A/B runs
+        mode = os.environ.get("GYMFLOCK_NET_STORE")
+        if mode:
+            if mode not in ("full", "delta"):
+                raise ValueError("GYMFLOCK_NET_STORE must be 'full' or 'delta', not %r" % mode)
+            if hasattr(self.lib, "fe_set_network_store"):  # (an older library of an A/B run has none)
+                self.set_network_store(FE_NET_FULL if mode == "full" else FE_NET_DELTA)
+
+    def set_network_store(self, mode):
+        """FE_NET_DELTA (default): the plain step stores only the groups of the dense
+        network that changed; FE_NET_FULL: every step stores it in full."""
+        check(self.lib.fe_set_network_store(self.h, int(mode)))
+
+    def network_touched(self):
+        """Tell the library that the caller wrote into device_buffers().network: the next
+        step stores it in full (fe_network_touched)."""
+        check(self.lib.fe_network_touched(self.h))
 
     def close(self):
         h = getattr(self, "h", None)

@@ -252,6 +252,28 @@ int fe_host_alloc(size_t bytes, void** out);
 int fe_host_free(void* p);               /* (B)   :145-147 */
 int fe_get_knn(fe_handle* h, int env, int32_t* idx, float* obs); /* (N,k), (N,4k) */
 int fe_device_buffers(fe_handle* h, fe_buffers* out);
+/* How the plain step (no controller, variant, kNN or inline host actions; N % 4 == 0)
+ * stores the dense network into the handle's buffer. The buffer holds the same dense
+ * float32 network either way, bit for bit.
+ *  FE_NET_DELTA (default): the library keeps a record of what the buffer holds (33 MiB at
+ *    1024 x 256) and a step stores only the groups of the rows whose content changes.
+ *    Every other kind of step stores in full, after which the next plain step stores in
+ *    full once more to rebuild the record.
+ *  FE_NET_FULL: every step stores every row in full and no record is kept.
+ * The record costs a read and a write of N^2/8 bytes per env beside the 4 N^2 of the
+ * network: where most groups change every step (a mean degree above N/4, where nearly
+ * every 64-byte group holds a neighbour) the delta store moves up to 6.25 % more bytes
+ * than the full one; choose FE_NET_FULL there. Measured on one MI355X at 1024 x 256
+ * (profiles/delta_store/synthetic_full_vs_delta.json): a flock of mean degree 263 with
+ * random actions runs 271.9 us per step with the delta store against 263.8 us in full
+ * (3.1 % slower); nothing changing at all 142.9 against 170.2 us; the bench workload
+ * 130.3 against 159.5 us ("Delta network store").
+ * fe_buffers.network is read-only to callers: one that writes into it must call
+ * fe_network_touched() before the next step, which then stores in full. */
+#define FE_NET_DELTA 0
+#define FE_NET_FULL 1
+int fe_set_network_store(fe_handle* h, int mode);
+int fe_network_touched(fe_handle* h);
 int fe_sync(fe_handle* h);
 /* Select a flocking variant for every later step / controller call (NULL: back to
  * FlockingRelative). */
