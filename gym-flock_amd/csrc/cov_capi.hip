@@ -602,6 +602,9 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
     return fail(GF_EINVAL, "map_seed + n_envs must fit in 32 bits (np.random.seed)");
   if (!given && !(flags & COV_MAP_SEED) && !h->map_seeded)
     return fail(GF_ESTATE, "the envs' map streams were never seeded (COV_MAP_SEED)");
+  if (given)
+    for (size_t q = 0, nq = (size_t)(env < 0 ? B : 1) * NC * 2; q < nq; ++q)
+      if (!std::isfinite(cities[q])) return fail(GF_EINVAL, "map: the given cities hold a NaN or an infinity");
   if (int rc = use(h)) return rc;
   int rc;
   if ((rc = ensure_map_buffers(h))) return rc;
@@ -610,7 +613,11 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
   // 3 NC - 6 of them, none longer than the cities' square's diagonal), within the LDS left
   const double diag = 2.0 * std::sqrt(2.0) * mc->world_radius;
   const double wbound = NC + (3.0 * NC - 6.0) * (std::floor(diag / mc->road_radius) + 1.0);
-  const size_t lds_max = 150 * 1024, lds_lat = (size_t)h->lat_L * 12;
+  // (a degenerate city set can have up to NC (NC - 1) / 2 roads and more waypoints than this
+  // general-position bound: the kernel holds every road and reports such a map as OVERFLOW).
+  // 145 KB dynamic: the kernel's static LDS (7.5 KB, the roads of all 496 city pairs
+  // included) comes on top, within the CU's 160 KB
+  const size_t lds_max = 145 * 1024, lds_lat = (size_t)h->lat_L * 12;
   if (lds_lat + 64 * 16 > lds_max) return fail(GF_EINVAL, "map: lattice too large for the LDS");
   // the waypoint grid of the near-road test: cells of side near_radius (1 + 2^-20) over the
   // cities' square and the arena, one cell of margin; without room for it (or for an odd

@@ -25,9 +25,9 @@
 //
 // One workgroup of 512 threads per env. The lattice (1,849 points at the defaults) is
 // the same for every env and read through L2; waypoints, near flags, the union-find
-// forest and the component counts live in LDS (~68 KB at the defaults). The link search
-// walks the lattice's cell grid (a square lattice: K cells either side cover the link
-// radius), not all pairs.
+// forest and the component counts live in LDS (~71 KB at the defaults, 7.5 KB of it
+// static). The link search walks the lattice's cell grid (a square lattice: K cells either
+// side cover the link radius), not all pairs.
 #include "coverage_internal.h"
 
 namespace gf {
@@ -36,6 +36,11 @@ namespace {
 
 constexpr int kMapThreads = 512;
 constexpr int kMapWaves = kMapThreads / 64;
+// Every pair of cities can be a road: a planar triangulation has at most 3 NC - 6 edges, but
+// cocircular cities leave every triple's circumcircle empty, and all their pairs are kept.
+constexpr int kMapMaxEdges = kMapMaxCities * (kMapMaxCities - 1) / 2;
+static_assert(kMapMaxEdges <= kMapThreads, "one thread per road in step 3");
+static_assert(kMapMaxCities <= 256, "elist holds city indices in bytes");
 constexpr double kEps = 1.1102230246251565e-16;  // 2^-53
 constexpr double kIccBound = 4.0 * (10.0 + 96.0 * kEps) * kEps;
 constexpr double kCcwBound = 4.0 * (3.0 + 16.0 * kEps) * kEps;
@@ -86,9 +91,9 @@ __global__ __launch_bounds__(kMapThreads) void cov_map_kernel(CovMapArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ double2 city[kMapMaxCities];
   __shared__ uint32_t adj[kMapMaxCities];
-  __shared__ int2 elist[3 * kMapMaxCities];
-  __shared__ int eoff[3 * kMapMaxCities + 1];
-  __shared__ double edist[3 * kMapMaxCities];
+  __shared__ uchar2 elist[kMapMaxEdges];
+  __shared__ int eoff[kMapMaxEdges + 1];
+  __shared__ double edist[kMapMaxEdges];
   __shared__ int wsum[kMapWaves + 1];
   __shared__ int nedge_s, flags_s;
   __shared__ unsigned long long best_s;
@@ -160,10 +165,10 @@ __global__ __launch_bounds__(kMapThreads) void cov_map_kernel(CovMapArgs a) {
   __syncthreads();
   // 3. the roads (i < j, the reference's edge order; the order does not matter below)
   if (tid == 0) {
-    int n = 0;
+    int n = 0;  // at most NC (NC - 1) / 2 <= kMapMaxEdges: no road is dropped
     for (int i = 0; i < NC; ++i)
       for (int j = i + 1; j < NC; ++j)
-        if (((adj[i] >> j) & 1u) && n < 3 * kMapMaxCities) elist[n++] = make_int2(i, j);
+        if ((adj[i] >> j) & 1u) elist[n++] = make_uchar2((unsigned char)i, (unsigned char)j);
     nedge_s = n;
   }
   __syncthreads();
@@ -173,7 +178,11 @@ __global__ __launch_bounds__(kMapThreads) void cov_map_kernel(CovMapArgs a) {
     const double dx = p1.x - p2.x, dy = p1.y - p2.y;
     const double dist = sqrt(__fma_rn(dy, dy, dx * dx));
     edist[tid] = dist;
-    eoff[tid + 1] = static_cast<int>(dist / a.road_radius);
+    // int(dist / road_radius), decided in double before the conversion: a count above the
+    // capacity, or a NaN (a NaN or infinite city), becomes wcap + 1, which the sum below
+    // reports as an overflow and which, times kMapMaxEdges, stays far inside an int
+    const double cnt = dist / a.road_radius;
+    eoff[tid + 1] = cnt <= static_cast<double>(a.wcap) ? static_cast<int>(cnt) : a.wcap + 1;
   }
   __syncthreads();
   if (tid == 0) {

@@ -412,14 +412,25 @@ typedef struct cov_map_config {
                                        its own precision handling (parity unpinned)         */
 #define COV_MAP_TOO_MANY        0x2 /* more targets than max_nodes - n_robots              */
 #define COV_MAP_TOO_FEW         0x4 /* fewer targets than robots                           */
-#define COV_MAP_OVERFLOW        0x8 /* more waypoints than the kernel holds                */
+#define COV_MAP_OVERFLOW        0x8 /* more waypoints than the kernel holds: its capacity is
+                                       the bound for cities in general position inside
+                                       world_radius (n_cities + (3 n_cities - 6) roads of at
+                                       most the square's diagonal), less if the LDS is
+                                       short. Cocircular cities (up to n (n - 1) / 2 roads,
+                                       all of them kept), given cities outside
+                                       world_radius or a tiny road_radius can exceed it;
+                                       a road whose waypoint count is above it, not a
+                                       number or beyond an int is reported the same way */
 /* New maps on the device for env `env` (env < 0: every env): the cities (drawn on the
  * device from each env's stream, numpy's legacy uniform, or given), their Delaunay roads,
  * the lattice points near them and the largest connected component of their radius
  * graph; then the motion graph and static observation as cov_set_targets builds them.
  * n_targets_out, status_out (n_sel) and cities_out (n_sel, n_cities, 2) may be NULL. A
  * map that cannot be used (TOO_MANY / TOO_FEW / OVERFLOW) fails the call with GF_EINVAL,
- * that env left without a graph; NEAR_DEGENERATE maps are used and reported. */
+ * that env left without a graph; NEAR_DEGENERATE maps are used and reported. A map is
+ * never built from a shortened road list: every pair of up to 32 cities can be a road (the
+ * cocircular case), and a map whose waypoints do not fit is OVERFLOW. Given cities must be
+ * finite: a NaN or an infinity fails the call with GF_EINVAL before anything is launched. */
 int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t map_seed, const double* cities,
                       int flags, int32_t* n_targets_out, int32_t* status_out, double* cities_out);
 /* The targets (n_targets, 2) of env `env`'s current map. */
