@@ -46,6 +46,11 @@ struct cov_handle {
   uint16_t* tm_glen = nullptr;   // (B,Tmax)
   int gstride = 0;
   uint8_t* tm_flags = nullptr;
+  size_t tm_flags_bytes = 0;     // grown when a plan takes narrower tiles (more chunks per env)
+  int32_t* tm_sched_scratch = nullptr;  // the schedule kernel's edges and levels when they exceed the LDS
+  size_t tm_sched_scratch_words = 0;
+  int tm_plan_s = 0;             // cov_set_tm_plan: sources per wave (0: the largest that fits)
+  int tm_plan_global = 0;        //   1: the schedule's edges and levels in the global scratch
   uint8_t* needs_random = nullptr;
   int32_t* tm_envsel = nullptr;
   uint32_t* tm_sched = nullptr;
@@ -147,7 +152,7 @@ void cov_release(cov_handle* h) {
   void* bufs[] = {h->ntg, h->tgt, a.nbr, a.cnt, a.n_motion, a.xr, a.cur, a.visited, a.nvisited,
                   a.step_counter, a.dirty, h->actions, a.reward, a.done, a.nodes, a.edges, a.senders,
                   a.receivers, a.obs_step, a.axy, a.nrec, h->err, h->start, h->visited0, h->envsel, h->tm_cost, h->tm_cost8, h->tm_wide, h->tm_prevT, h->tm_glist, h->tm_glen,
-                  h->tm_flags, h->needs_random, h->tm_envsel, h->tm_sched, h->tm_lev, h->tm_nslots, h->tm_nlev, h->tm_overflow, h->scratch,
+                  h->tm_flags, h->tm_sched_scratch, h->needs_random, h->tm_envsel, h->tm_sched, h->tm_lev, h->tm_nslots, h->tm_nlev, h->tm_overflow, h->scratch,
                   h->goff, h->mt_key, h->mt_pos, h->map_key, h->map_pos, h->map_cities, h->map_nraw,
                   h->map_status, h->lat, h->lat_cell, h->lat_grid, h->occ_grid, h->pool_cellmap, h->pool_rawcell,
                   h->pool_raw, h->pool_xy, h->pool_cell, h->pool_info, h->pool_counts, h->sub_tries,
@@ -187,16 +192,33 @@ int copy_out(cov_handle* h, void* dst, const void* src, size_t bytes) {
   return GF_OK;
 }
 
+// The time-matrix flags (B, nchunk, kcap) for tiles of S sources per wave.
+int ensure_tm_flags(cov_handle* h, int S, int kcap) {
+  const size_t need = (size_t)h->cfg.n_envs * ((h->a.Tmax + S - 1) / S) * kcap;
+  if (need <= h->tm_flags_bytes) return GF_OK;
+  if (h->tm_flags) GF_HIP(hipFree(h->tm_flags));
+  h->tm_flags = nullptr;
+  h->tm_flags_bytes = 0;
+  if (int rc = dalloc_zero(&h->tm_flags, need)) return rc;
+  h->tm_flags_bytes = need;
+  return GF_OK;
+}
+
+// Sources per wave for a time-matrix pass over maps of up to t_lds targets: the plan's
+// (cov_set_tm_plan, narrowed where this launch's maps need it) or the largest whose tile fits.
+int tm_sources(const cov_handle* h, int t_lds, bool wide) {
+  const int fit = gf::cov_time_matrix_sources(t_lds, wide);
+  return h->tm_plan_s ? std::min(h->tm_plan_s, fit) : fit;
+}
+
 // Time matrices of every env whose graph changed since they were last built.
 int ensure_time_matrix(cov_handle* h) {
   const int B = h->cfg.n_envs, Tm = h->a.Tmax;
   const int kcap = h->cfg.horizon > -1 ? h->cfg.horizon + 1 : Tm + 1;
-  const int nchunk = (Tm + 63) / 64;
   const int sched_stride = 4 * Tm * 16 + 16;  // motion edges <= 4 per target, batches <= 16, + prefetch slack
   if (!h->tm_cost) {
     int rc;
     if ((rc = dalloc_zero(&h->tm_cost, (size_t)B * Tm * Tm)) || (rc = dalloc_zero(&h->tm_prevT, (size_t)B * Tm * Tm)) ||
-        (rc = dalloc_zero(&h->tm_flags, (size_t)B * nchunk * kcap)) ||
         (rc = dalloc_zero(&h->needs_random, (size_t)B * h->cfg.n_robots)) || (rc = dalloc_zero(&h->tm_envsel, (size_t)B)) ||
         (rc = dalloc_zero(&h->tm_sched, (size_t)B * sched_stride)) || (rc = dalloc_zero(&h->tm_nslots, (size_t)B)) ||
         (rc = dalloc_zero(&h->tm_lev, (size_t)B * (4 * Tm + 2))) ||
@@ -222,16 +244,32 @@ int ensure_time_matrix(cov_handle* h) {
     h->tm_ready = true;
     return GF_OK;
   }
-  if (gf::cov_time_matrix_lds_bytes(t_lds, false) > 160 * 1024 ||
-      gf::cov_tm_schedule_lds_bytes(t_lds, e_max) > 160 * 1024)
-    return fail(GF_EINVAL, "time matrix: (n_targets + 1) * 64 bytes exceed the 160 KB LDS of a CU");
+  if (t_lds > COV_POOL_CAP)
+    return fail(GF_EINVAL, "time matrix: a map has " + std::to_string(t_lds) + " targets, more than the " +
+                               std::to_string(COV_POOL_CAP) + " the expert supports");
+  // sources per wave: the widest LDS tile that holds the launch's largest map
+  const int s8 = tm_sources(h, t_lds, false);
+  if (int rc = ensure_tm_flags(h, s8, kcap)) return rc;
+  // the schedule's edges and levels: in LDS while they fit beside the columns' state
+  const bool sched_global = h->tm_plan_global || gf::cov_tm_schedule_lds_bytes(t_lds, e_max, false) > 160 * 1024;
+  const int scratch_stride = 4 * e_max + 2;
+  if (sched_global && sel.size() * (size_t)scratch_stride > h->tm_sched_scratch_words) {
+    if (h->tm_sched_scratch) GF_HIP(hipFree(h->tm_sched_scratch));
+    h->tm_sched_scratch = nullptr;
+    h->tm_sched_scratch_words = 0;
+    if (int rc = dalloc_zero(&h->tm_sched_scratch, sel.size() * (size_t)scratch_stride)) return rc;
+    h->tm_sched_scratch_words = sel.size() * (size_t)scratch_stride;
+  }
   gf::CovTmArgs t{};
   t.R = h->a.R;
   t.M = h->a.M;
   t.Tmax = Tm;
   t.horizon = h->cfg.horizon;
   t.kcap = kcap;
-  t.nchunk = nchunk;
+  t.tm_s = s8;
+  t.nchunk = (Tm + s8 - 1) / s8;
+  t.sched_scratch = sched_global ? h->tm_sched_scratch : nullptr;
+  t.scratch_stride = scratch_stride;
   t.t_lds = t_lds;
   t.envs = h->tm_envsel;
   t.ntg = h->ntg;
@@ -266,8 +304,11 @@ int ensure_time_matrix(cov_handle* h) {
       t_wide = std::max(t_wide, h->ntg_host[b]);
     }
   if (!wide.empty()) {
-    if (gf::cov_time_matrix_lds_bytes(t_wide, true) > 160 * 1024)
-      return fail(GF_EINVAL, "time matrix: hop counts above 254 need (n_targets + 1) * 128 bytes of LDS (> 160 KB)");
+    const int s16 = tm_sources(h, t_wide, true);
+    if (int rc = ensure_tm_flags(h, s16, kcap)) return rc;
+    t.flags = h->tm_flags;
+    t.tm_s = s16;
+    t.nchunk = (Tm + s16 - 1) / s16;
     GF_HIP(hipMemsetAsync(h->tm_overflow, 0, B, h->stream));
     GF_HIP(hipMemcpyAsync(h->tm_envsel, wide.data(), wide.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     t.t_lds = t_wide;
@@ -959,7 +1000,7 @@ int cov_reset_seeded(cov_handle* h, uint64_t seed, double frac_active, int32_t* 
   const size_t B = h->cfg.n_envs, R = h->cfg.n_robots, Tm = h->a.Tmax;
   if (seed + B > 0x100000000ull) return fail(GF_EINVAL, "seed + n_envs must fit in 32 bits (RandomState seeds)");
   if (!(frac_active >= 0.0 && frac_active <= 1.0)) return fail(GF_EINVAL, "frac_active must be in [0, 1]");
-  if ((size_t)gf::kMtN * 4 + Tm * 5 > 65536)  // the draw kernel's LDS: key, permutation, flags
+  if (gf::cov_seed_reset_lds_bytes((int)Tm) > 160 * 1024)  // the draw kernel's LDS: key, permutation, draws, flags
     return fail(GF_EINVAL, "max_nodes - n_robots too large for the device reset draws (draw on the host)");
   if (int rc = use(h)) return rc;
   if (!h->mt_key) {
@@ -1595,6 +1636,23 @@ int cov_set_streams(cov_handle* h, int n) {
   if (!h || n < 0 || n > 2) return fail(GF_EINVAL, "n must be 0 (auto), 1 or 2");
   if (int rc = use(h)) return rc;
   h->nsplit = n;
+  return GF_OK;
+}
+
+int cov_set_tm_plan(cov_handle* h, int sources_per_wave, int schedule_in_global) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  const int S = sources_per_wave;
+  if (S != 0 && S != 8 && S != 16 && S != 32 && S != 64) return fail(GF_EINVAL, "sources_per_wave must be 0 (auto), 8, 16, 32 or 64");
+  if (schedule_in_global != 0 && schedule_in_global != 1) return fail(GF_EINVAL, "schedule_in_global must be 0 or 1");
+  // the uint8 tile of the largest map the handle can hold (the uint16 rerun narrows it where it must)
+  if (S && gf::cov_time_matrix_lds_bytes(h->a.Tmax, false, S) > 160 * 1024)
+    return fail(GF_EINVAL, "sources_per_wave: (max_nodes - n_robots + 1) * " + std::to_string(S) +
+                               " bytes exceed the 160 KB LDS of a CU");
+  if (int rc = use(h)) return rc;
+  h->tm_plan_s = S;
+  h->tm_plan_global = schedule_in_global;
+  std::fill(h->tm_valid.begin(), h->tm_valid.end(), 0);
+  h->tm_ready = false;
   return GF_OK;
 }
 

@@ -38,8 +38,9 @@ constexpr int kArlThreads = 512;
 constexpr int kArlWaves = kArlThreads / 64;
 
 __global__ __launch_bounds__(kArlThreads) void cov_pool_kernel(CovPoolArgs a) {
-  __shared__ int32_t parent[kPoolCap];
-  __shared__ int32_t cnt[kPoolCap];
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int32_t* parent = reinterpret_cast<int32_t*>(smem);  // (kPoolCap) union-find forest
+  int32_t* cnt = parent + kPoolCap;                    // (kPoolCap) component sizes by root
   __shared__ int wsum[kArlWaves + 1];
   __shared__ unsigned long long best_s;
   __shared__ double red[kArlWaves][4];
@@ -322,7 +323,11 @@ __global__ __launch_bounds__(kArlThreads) void cov_submap_kernel(CovSubmapArgs a
 size_t cov_submap_lds_bytes(int P) { return (size_t)P * 16; }
 
 hipError_t launch_cov_pool(const CovPoolArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(cov_pool_kernel, dim3(1), dim3(kArlThreads), 0, s, a);
+  const size_t lds = (size_t)kPoolCap * 8;  // parent, cnt
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cov_pool_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(cov_pool_kernel, dim3(1), dim3(kArlThreads), lds, s, a);
   return hipGetLastError();
 }
 

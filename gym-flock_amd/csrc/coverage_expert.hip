@@ -8,8 +8,10 @@
 // entry changed AND some entry is still infinite, at most horizon+1 sweeps. Rows
 // (sources) are independent within a sweep; only the stop rule couples them. So:
 //   - one wave per 64 sources of one env; each lane owns one source's row, kept in LDS
-//     as uint16 (0xFFFF = inf) in column-major order, so a lane only ever touches its
-//     own entries and a sweep needs no barrier;
+//     as uint8 or uint16 (all ones = inf) in column-major order, so a lane only ever
+//     touches its own entries and a sweep needs no barrier. Maps whose 64-source tile
+//     exceeds the LDS (above 2,559 targets; up to 8,192) take 32, 16 or 8 sources per
+//     wave, the freed lanes sharing each batch's edges (cov_time_matrix_kernel);
 //   - edge order within a sweep: two relaxations commute unless one writes a column
 //     the other reads or writes, so any order that keeps every such pair in list order
 //     gives bit-identical results (tests/test_coverage_greedy_gpu.py checks it against
@@ -33,7 +35,8 @@ namespace {
 #ifndef GF_TM_DIAG
 #define GF_TM_DIAG 0  // timing ablations only (wrong results): 1 no early stop, 2 schedule window, 4 no predecessor stores
 #endif
-constexpr int kTmLanes = 64;            // sources per wave (one wave per workgroup)
+constexpr int kTmLanes = 64;            // lanes of the wave (one wave per workgroup); the most sources per wave
+constexpr size_t kTmLdsMax = 160 * 1024;  // a CU's LDS
 constexpr int kBatch = 8;               // independent edges per batch (16 measured slower)
 constexpr uint32_t kInf = 0xFFFF;  // uint16 cost matrix: unreachable
 constexpr int kMaxCost = 1000;          // MAX_COST :68
@@ -44,6 +47,29 @@ constexpr int kMaxCost = 1000;          // MAX_COST :68
 // time (below); the counts, offsets and the scatter run on the whole wave. Edges of one
 // level are mutually independent, so their order inside the level does not change any
 // result.
+//
+// GLOBAL (maps whose (2T + 4E + 4) words exceed the LDS): only the columns' state lw / lr
+// stays in LDS; the edges and their levels live in a scratch of 4E + 2 words per selected
+// env, read and written past the L1 (a plain load could return a line fetched before a
+// later atomic). Once the levels are known the columns' state is dead, so the per-level
+// counts and offsets take its place whenever the level count fits (nlev < T, every map
+// seen so far: the scatter's LDS atomics then run in lane order as in the LDS form, and
+// the schedule is the same word for word); else they go to the scratch too, where the
+// order inside a level may differ (any order of a level gives the same matrices).
+template <bool GLOBAL>
+__device__ __forceinline__ int sch_ld(const int* p) {
+  if (GLOBAL) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return *p;
+}
+template <bool GLOBAL>
+__device__ __forceinline__ void sch_st(int* p, int v) {
+  if (GLOBAL)
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else
+    *p = v;
+}
+
+template <bool GLOBAL>
 __global__ __launch_bounds__(64) void cov_tm_schedule_kernel(CovTmArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = a.envs[blockIdx.x];
@@ -52,15 +78,18 @@ __global__ __launch_bounds__(64) void cov_tm_schedule_kernel(CovTmArgs a) {
   int* shared2 = reinterpret_cast<int*>(smem);  // the level count, the slot count
   int* lw = shared2 + 2;                          // [T] last level writing the column
   int* lr = lw + T;                               // [T] last level reading it
-  uint32_t* sq = reinterpret_cast<uint32_t*>(lr + T);  // [E] the edges, s | q << 16
-  int* level = reinterpret_cast<int*>(sq + E);          // [E]
-  int* fill = level + E;                                // [E + 1] per-level counts, then offsets
-  int* base = fill + E + 1;                             // [E + 1] the levels' padded offsets
+  int* gs = GLOBAL ? a.sched_scratch + (size_t)blockIdx.x * a.scratch_stride : lr + T;
+  int* sq = gs;           // [E] the edges, s | q << 16
+  int* level = sq + E;    // [E]
+  int* fill = level + E;  // [E + 1] per-level counts, then offsets
+  int* base = fill + E + 1;  // [E + 1] the levels' padded offsets
   const int32_t* snd = a.senders + (size_t)b * E4;
   const int32_t* rcv = a.receivers + (size_t)b * E4;
   for (int k = lane; k < T; k += 64) lw[k] = lr[k] = 0;
-  for (int k = lane; k <= E; k += 64) fill[k] = 0;
-  for (int e = lane; e < E; e += 64) sq[e] = (uint32_t)(snd[e] - R) | ((uint32_t)(rcv[e] - R) << 16);
+  if (!GLOBAL)
+    for (int k = lane; k <= E; k += 64) fill[k] = 0;
+  for (int e = lane; e < E; e += 64)
+    sch_st<GLOBAL>(&sq[e], (int)((uint32_t)(snd[e] - R) | ((uint32_t)(rcv[e] - R) << 16)));
   __syncthreads();
   // 64 edges at a time, lane i taking edge e0 + i: its level from the columns' state
   // before the window, then raised past every earlier edge of the window it conflicts
@@ -70,7 +99,7 @@ __global__ __launch_bounds__(64) void cov_tm_schedule_kernel(CovTmArgs a) {
   for (int e0 = 0; e0 < E; e0 += 64) {
     const int e = e0 + lane;
     const bool ve = e < E;
-    const uint32_t w = ve ? sq[e] : 0xFFFEFFFFu;  // past E: columns no edge has
+    const uint32_t w = ve ? (uint32_t)sch_ld<GLOBAL>(&sq[e]) : 0xFFFEFFFFu;  // past E: columns no edge has
     const int s = w & 0xFFFF, q = w >> 16;
     int L = ve ? max(max(lw[s], lw[q]), lr[q]) + 1 : 0;
     const int n = min(64, E - e0);
@@ -82,7 +111,7 @@ __global__ __launch_bounds__(64) void cov_tm_schedule_kernel(CovTmArgs a) {
     }
     __syncthreads();  // every lane has read the state the window started from
     if (ve) {
-      level[e] = L;
+      sch_st<GLOBAL>(&level[e], L);
       atomicMax(&lw[q], L);
       atomicMax(&lr[s], L);
       atomicMax(&lr[q], L);
@@ -94,29 +123,39 @@ __global__ __launch_bounds__(64) void cov_tm_schedule_kernel(CovTmArgs a) {
   if (lane == 0) shared2[0] = nlev_w;
   __syncthreads();
   const int nlev = shared2[0];
-  for (int e = lane; e < E; e += 64) atomicAdd(&fill[level[e] - 1], 1);
+  if (GLOBAL) {
+    if (nlev < T) {  // uniform: the counts and offsets over the dead column state
+      fill = lw;
+      base = lr;
+    }
+    for (int k = lane; k <= nlev; k += 64) sch_st<GLOBAL>(&fill[k], 0);
+    __syncthreads();
+  }
+  for (int e = lane; e < E; e += 64) atomicAdd(&fill[sch_ld<GLOBAL>(&level[e]) - 1], 1);
   __syncthreads();
   if (lane == 0) {
     int off = 0;
     for (int L = 0; L < nlev; ++L) {
-      const int n = fill[L];
-      fill[L] = base[L] = off;
+      const int n = sch_ld<GLOBAL>(&fill[L]);
+      sch_st<GLOBAL>(&fill[L], off);
+      sch_st<GLOBAL>(&base[L], off);
       off += (n + kBatch - 1) / kBatch * kBatch;
     }
-    base[nlev] = off;
+    sch_st<GLOBAL>(&base[nlev], off);
     shared2[1] = off;
   }
   __syncthreads();
   const int off = shared2[1];
   uint32_t* out = a.sched + (size_t)b * a.sched_stride;
-  for (int e = lane; e < E; e += 64) out[atomicAdd(&fill[level[e] - 1], 1)] = sq[e];
+  for (int e = lane; e < E; e += 64)
+    out[atomicAdd(&fill[sch_ld<GLOBAL>(&level[e]) - 1], 1)] = (uint32_t)sch_ld<GLOBAL>(&sq[e]);
   __syncthreads();
   // each level's padding (past its edges) holds no-ops: words no edge was stored to
   const uint32_t noop = (uint32_t)T | ((uint32_t)T << 16);
   for (int L = lane; L < nlev; L += 64)
-    for (int k = fill[L]; k < base[L + 1]; ++k) out[k] = noop;
+    for (int k = sch_ld<GLOBAL>(&fill[L]), k1 = sch_ld<GLOBAL>(&base[L + 1]); k < k1; ++k) out[k] = noop;
   if (a.lev_off)  // the levels' slot offsets (cov_time_matrix_mw_kernel)
-    for (int L = lane; L <= nlev; L += 64) a.lev_off[(size_t)b * a.lev_stride + L] = base[L];
+    for (int L = lane; L <= nlev; L += 64) a.lev_off[(size_t)b * a.lev_stride + L] = sch_ld<GLOBAL>(&base[L]);
   if (lane == 0) {
     a.nslots[b] = off;
     a.nlev[b] = nlev;
@@ -124,37 +163,56 @@ __global__ __launch_bounds__(64) void cov_tm_schedule_kernel(CovTmArgs a) {
   }
 }
 
-// Per-lane scan of its own row after a sweep: any entry still inf, and the largest
-// finite entry (the uint8 variant's overflow guard).
-template <typename V>
-__device__ __forceinline__ void tm_scan(const V* col, int T, int lane, bool valid, bool& any_inf, uint32_t& mx) {
+// Per-lane scan of its share of its source's row after a sweep (every G-th column from g;
+// S = 64: the whole row): any entry still inf, and the largest finite entry (the uint8
+// variant's overflow guard). The callers combine the lanes by ballot.
+template <typename V, int S>
+__device__ __forceinline__ void tm_scan(const V* col, int T, int sl, int g, bool valid, bool& any_inf, uint32_t& mx) {
   constexpr uint32_t inf = (V)~(V)0;
+  constexpr int G = kTmLanes / S;
   any_inf = false;
   mx = 0;
   if (!valid) return;
-  for (int t = 0; t < T; ++t) {
-    const uint32_t v = col[t * kTmLanes + lane];
+  for (int t = g; t < T; t += G) {
+    const uint32_t v = col[t * S + sl];
     any_inf = any_inf || v == inf;
     mx = v != inf && v > mx ? v : mx;
   }
 }
 
-// Time matrix of one 64-source chunk with entries of type V (uint8_t: inf = 255;
+// Time matrix of one S-source chunk with entries of type V (uint8_t: inf = 255;
 // uint16_t: inf = 0xFFFF). One sweep raises the largest finite entry by at most the
 // schedule's level count (a value moves one hop per level), so the uint8 variant runs a
 // sweep only while max + nlev < 255 and otherwise flags the env for the uint16 rerun.
-template <typename V, bool PASS_B>
+//
+// S = 64, 32, 16 or 8 sources per wave is the column stride of the LDS tile [T + 1][S]:
+// maps whose tile of 64 sources exceeds the LDS take a narrower one. The lanes a narrower
+// tile frees are not idle: a batch's 8 edges are mutually independent (disjoint written
+// columns, none read by another; no-ops all rewrite inf on the dummy column), so lane l
+// serves source l % S and the batch's slots g, g + G, ... with g = l / S, G = 64 / S
+// (one edge per lane at S = 8, two at 16, four at 32), reading its schedule words itself
+// where S = 64 broadcasts them. The wave's LDS and memory operations stay in program
+// order, so batches follow each other as before; the `changed` and `inf` ballots, the
+// overflow guard and the store skip are over the wave and keep their meaning; the row
+// scan, the predecessors' -1 fill and the row stores are split over the G lanes of a
+// source. S = 64 is the kernel as it was.
+template <typename V, bool PASS_B, int S>
 __global__ __launch_bounds__(kTmLanes) void cov_time_matrix_kernel(CovTmArgs a, const uint32_t* __restrict__ sched_all) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr uint32_t inf = (V)~(V)0;
+  constexpr int G = kTmLanes / S;    // lane groups: slots of a batch served at once
+  constexpr int EPL = kBatch / G;    // edges per lane and batch
+  static_assert(S * G == kTmLanes && EPL * G == kBatch, "S divides the wave, G the batch");
   const int b = a.envs[blockIdx.y];
   const int chunk = blockIdx.x;
   const int T = a.ntg[b];
-  const int src0 = chunk * kTmLanes;
+  const int src0 = chunk * S;
   if (src0 >= T) return;  // uniform
   const int Tm = a.Tmax;
   const int lane = threadIdx.x;
-  const int src = src0 + lane;
+  const int sl = S == kTmLanes ? lane : lane & (S - 1);  // the lane's source in the tile
+  const int g = S == kTmLanes ? 0 : lane / S;            // its first slot in a batch
+  const int src = src0 + sl;
   const bool valid = src < T;
   const int kmax = a.horizon > -1 ? a.horizon + 1 : a.kcap;
   const int nlev = a.nlev[b];
@@ -165,7 +223,7 @@ __global__ __launch_bounds__(kTmLanes) void cov_time_matrix_kernel(CovTmArgs a, 
     // the reference's sweep count: stop after sweep k once no entry of the env changed
     // or none is infinite (the while test), or after horizon+1 sweeps (the break)
     const uint8_t* fenv = a.flags + (size_t)b * a.nchunk * a.kcap;
-    const int nch = (T + kTmLanes - 1) / kTmLanes;
+    const int nch = (T + S - 1) / S;
     for (int k = 0; k < kmax && K == kmax && T > 1; ++k) {
       int f = 0;
       for (int c = 0; c < nch; ++c) f |= fenv[(size_t)c * a.kcap + k];
@@ -181,14 +239,18 @@ __global__ __launch_bounds__(kTmLanes) void cov_time_matrix_kernel(CovTmArgs a, 
       }
     if (T <= 1 || K >= kvalid) return;
   }
-  V* col = reinterpret_cast<V*>(smem);  // [T + 1][64], column T = dummy inf
-  for (int t = 0; t <= T; ++t) col[t * kTmLanes + lane] = (t == src) ? 0 : (V)inf;
+  V* col = reinterpret_cast<V*>(smem);  // [T + 1][S], column T = dummy inf
   int16_t* prevT = a.prevT + (size_t)b * Tm * Tm;  // [q][src]
+  if (S == kTmLanes) {
+    for (int t = 0; t <= T; ++t) col[t * S + lane] = (t == src) ? 0 : (V)inf;
+  } else {
+    for (int t = g; t <= T; t += G) col[t * S + sl] = (t == src) ? 0 : (V)inf;
+  }
   // raw buffer over the env's [Tm][Tm] predecessors (stride 0: offsets range-checked
   // against Tm * Tm * 2 bytes; dword 3 = gfx9's data format)
   const __amdgpu_buffer_rsrc_t prv = __builtin_amdgcn_make_buffer_rsrc(prevT, 0, Tm * Tm * 2, 0x00020000);
   if (valid)
-    for (int q = 0; q < T; ++q) prevT[(size_t)q * Tm + src] = -1;
+    for (int q = g; q < T; q += G) prevT[(size_t)q * Tm + src] = -1;
   const uint32_t* sched = sched_all + (size_t)b * a.sched_stride;
   const int nslots = a.nslots[b];
   uint32_t mx = 0;
@@ -200,33 +262,33 @@ __global__ __launch_bounds__(kTmLanes) void cov_time_matrix_kernel(CovTmArgs a, 
       return;
     }
     int changed = 0;
-    uint32_t nxt[kBatch];
+    uint32_t nxt[EPL];
 #pragma unroll
-    for (int k = 0; k < kBatch; ++k) nxt[k] = sched[k];
+    for (int k = 0; k < EPL; ++k) nxt[k] = sched[g + k * G];
     for (int j = 0; j < nslots; j += kBatch) {
-      uint32_t w[kBatch];
+      uint32_t w[EPL];
 #pragma unroll
-      for (int k = 0; k < kBatch; ++k) w[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)nxt[k]);
+      for (int k = 0; k < EPL; ++k) w[k] = S == kTmLanes ? (uint32_t)__builtin_amdgcn_readfirstlane((int)nxt[k]) : nxt[k];
 #if GF_TM_DIAG & 2
 #pragma unroll
-      for (int k = 0; k < kBatch; ++k) nxt[k] = sched[((j + kBatch) & 56) + k];
+      for (int k = 0; k < EPL; ++k) nxt[k] = sched[((j + kBatch) & 56) + g + k * G];
 #else
 #pragma unroll
-      for (int k = 0; k < kBatch; ++k) nxt[k] = sched[j + kBatch + k];  // next batch (slack in the stride)
+      for (int k = 0; k < EPL; ++k) nxt[k] = sched[j + kBatch + g + k * G];  // next batch (slack in the stride)
 #endif
-      uint32_t vs[kBatch], vq[kBatch];
+      uint32_t vs[EPL], vq[EPL];
 #pragma unroll
-      for (int k = 0; k < kBatch; ++k) {
-        vs[k] = col[(w[k] & 0xFFFF) * kTmLanes + lane];
-        vq[k] = col[(w[k] >> 16) * kTmLanes + lane];
+      for (int k = 0; k < EPL; ++k) {
+        vs[k] = col[(w[k] & 0xFFFF) * S + sl];
+        vq[k] = col[(w[k] >> 16) * S + sl];
       }
-      bool better[kBatch];
+      bool better[EPL];
       bool bany = false;
 #pragma unroll
-      for (int k = 0; k < kBatch; ++k) {
+      for (int k = 0; k < EPL; ++k) {
         const uint32_t via = vs[k] + 1u;  // inf + 1 never wins
         better[k] = via < vq[k];
-        col[(w[k] >> 16) * kTmLanes + lane] = (V)(via < vq[k] ? via : vq[k]);
+        col[(w[k] >> 16) * S + sl] = (V)(via < vq[k] ? via : vq[k]);
         bany = bany || better[k];
       }
       changed |= bany ? 1 : 0;
@@ -238,7 +300,7 @@ __global__ __launch_bounds__(kTmLanes) void cov_time_matrix_kernel(CovTmArgs a, 
       // 8.54-8.58, and 16-edge schedule loads on top, 7.87-7.90, were slower)
       if (__ballot(bany) != 0) {
 #pragma unroll
-        for (int k = 0; k < kBatch; ++k) {
+        for (int k = 0; k < EPL; ++k) {
 #if !(GF_TM_DIAG & 4)
           __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(w[k] & 0xFFFF), prv,
                                                 better[k] ? (int)(((w[k] >> 16) * (uint32_t)Tm + src) * 2) : (int)0x7FFFFFF0,
@@ -249,7 +311,7 @@ __global__ __launch_bounds__(kTmLanes) void cov_time_matrix_kernel(CovTmArgs a, 
     }
     if (!PASS_B || sizeof(V) == 1) {
       bool any_inf_lane;
-      tm_scan(col, T, lane, valid, any_inf_lane, mx);
+      tm_scan<V, S>(col, T, sl, g, valid, any_inf_lane, mx);
       if (!PASS_B) {
         const bool any_changed = __ballot(changed) != 0;
         const bool any_inf = __ballot(any_inf_lane) != 0;
@@ -262,28 +324,47 @@ __global__ __launch_bounds__(kTmLanes) void cov_time_matrix_kernel(CovTmArgs a, 
     }
   }
   // cost rows, row-major [src][t] as uint16 (inf = 0xFFFF); 4 entries per 8-byte store
+  // (S < 64: the source's G lanes take the groups of 4, and of 8 for the uint8 copy, in turn)
   if (valid) {
     auto ent = [&](int t) -> uint64_t {
-      const uint32_t v = col[t * kTmLanes + lane];
+      const uint32_t v = col[t * S + sl];
       return v == inf ? 0xFFFFull : (uint64_t)v;
     };
     uint16_t* row = a.cost + ((size_t)b * Tm + src) * Tm;
-    int t = 0;
-    if ((Tm & 3) == 0)
-      for (; t + 4 <= T; t += 4)
+    if (S == kTmLanes) {
+      int t = 0;
+      if ((Tm & 3) == 0)
+        for (; t + 4 <= T; t += 4)
+          *reinterpret_cast<uint64_t*>(row + t) = ent(t) | (ent(t + 1) << 16) | (ent(t + 2) << 32) | (ent(t + 3) << 48);
+      for (; t < T; ++t) row[t] = (uint16_t)ent(t);
+    } else {
+      const int t4 = (Tm & 3) == 0 ? (T & ~3) : 0;
+      for (int t = 4 * g; t < t4; t += 4 * G)
         *reinterpret_cast<uint64_t*>(row + t) = ent(t) | (ent(t + 1) << 16) | (ent(t + 2) << 32) | (ent(t + 3) << 48);
-    for (; t < T; ++t) row[t] = (uint16_t)ent(t);
+      for (int t = t4 + g; t < T; t += G) row[t] = (uint16_t)ent(t);
+    }
     if (sizeof(V) == 1 && a.cost8) {  // the greedy step's copy: one byte per entry, inf = 255
       uint8_t* row8 = a.cost8 + ((size_t)b * Tm + src) * Tm;
-      t = 0;
-      if ((Tm & 7) == 0)
-        for (; t + 8 <= T; t += 8) {
+      if (S == kTmLanes) {
+        int t = 0;
+        if ((Tm & 7) == 0)
+          for (; t + 8 <= T; t += 8) {
+            uint64_t w = 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) w |= (uint64_t)col[(t + k) * S + lane] << (8 * k);
+            *reinterpret_cast<uint64_t*>(row8 + t) = w;
+          }
+        for (; t < T; ++t) row8[t] = (uint8_t)col[t * S + lane];
+      } else {
+        const int t8 = (Tm & 7) == 0 ? (T & ~7) : 0;
+        for (int t = 8 * g; t < t8; t += 8 * G) {
           uint64_t w = 0;
 #pragma unroll
-          for (int k = 0; k < 8; ++k) w |= (uint64_t)col[(t + k) * kTmLanes + lane] << (8 * k);
+          for (int k = 0; k < 8; ++k) w |= (uint64_t)col[(t + k) * S + sl] << (8 * k);
           *reinterpret_cast<uint64_t*>(row8 + t) = w;
         }
-      for (; t < T; ++t) row8[t] = (uint8_t)col[t * kTmLanes + lane];
+        for (int t = t8 + g; t < T; t += G) row8[t] = (uint8_t)col[t * S + sl];
+      }
     }
   }
 }
@@ -635,22 +716,60 @@ __global__ __launch_bounds__(256) void cov_greedy_kernel(CovGreedyArgs a) {
 
 }  // namespace
 
-size_t cov_time_matrix_lds_bytes(int t_lds, bool wide) { return (size_t)(t_lds + 1) * kTmLanes * (wide ? 2 : 1); }
+size_t cov_time_matrix_lds_bytes(int t_lds, bool wide, int S) { return (size_t)(t_lds + 1) * S * (wide ? 2 : 1); }
 
-size_t cov_tm_schedule_lds_bytes(int t_lds, int e_max) { return (size_t)(2 * t_lds + 4 * e_max + 4) * 4; }
+int cov_time_matrix_sources(int t_lds, bool wide) {
+  for (int S = kTmLanes; S >= 8; S >>= 1)
+    if (cov_time_matrix_lds_bytes(t_lds, wide, S) <= kTmLdsMax) return S;
+  return 0;
+}
+
+size_t cov_tm_schedule_lds_bytes(int t_lds, int e_max, bool global) {
+  return (size_t)(2 * t_lds + (global ? 0 : 4 * e_max) + 4) * 4;
+}
 
 hipError_t launch_cov_tm_schedule(const CovTmArgs& a, int n_envs_sel, int e_max, hipStream_t s) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cov_tm_schedule_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  const bool global = a.sched_scratch != nullptr;
+  const void* f = global ? reinterpret_cast<const void*>(&cov_tm_schedule_kernel<true>)
+                         : reinterpret_cast<const void*>(&cov_tm_schedule_kernel<false>);
+  hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTmLdsMax);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(cov_tm_schedule_kernel, dim3(n_envs_sel), dim3(64), cov_tm_schedule_lds_bytes(a.t_lds, e_max), s, a);
+  const size_t lds = cov_tm_schedule_lds_bytes(a.t_lds, e_max, global);
+  if (global)
+    hipLaunchKernelGGL(cov_tm_schedule_kernel<true>, dim3(n_envs_sel), dim3(64), lds, s, a);
+  else
+    hipLaunchKernelGGL(cov_tm_schedule_kernel<false>, dim3(n_envs_sel), dim3(64), lds, s, a);
+  return hipGetLastError();
+}
+
+// Pass A, then pass B, of the one-wave kernel with S sources per wave.
+template <typename V, int S>
+static hipError_t launch_tm_narrow(const CovTmArgs& a, int n_envs_sel, hipStream_t s) {
+  const dim3 grid((a.t_lds + S - 1) / S, n_envs_sel);
+  const size_t lds = cov_time_matrix_lds_bytes(a.t_lds, sizeof(V) == 2, S);
+  for (const void* f : {reinterpret_cast<const void*>(&cov_time_matrix_kernel<V, false, S>),
+                        reinterpret_cast<const void*>(&cov_time_matrix_kernel<V, true, S>)}) {
+    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTmLdsMax);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((cov_time_matrix_kernel<V, false, S>), grid, dim3(kTmLanes), lds, s, a, a.sched);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((cov_time_matrix_kernel<V, true, S>), grid, dim3(kTmLanes), lds, s, a, a.sched);
   return hipGetLastError();
 }
 
 template <typename V>
 static hipError_t launch_tm_passes(const CovTmArgs& a, int n_envs_sel, hipStream_t s) {
+  switch (a.tm_s) {
+    case 32: return launch_tm_narrow<V, 32>(a, n_envs_sel, s);
+    case 16: return launch_tm_narrow<V, 16>(a, n_envs_sel, s);
+    case 8: return launch_tm_narrow<V, 8>(a, n_envs_sel, s);
+    case kTmLanes: break;
+    default: return hipErrorInvalidValue;
+  }
   const dim3 grid((a.t_lds + kTmLanes - 1) / kTmLanes, n_envs_sel);
-  const size_t lds = cov_time_matrix_lds_bytes(a.t_lds, sizeof(V) == 2);
+  const size_t lds = cov_time_matrix_lds_bytes(a.t_lds, sizeof(V) == 2, kTmLanes);
   const size_t lds_mw = ((lds + 15) & ~(size_t)15) + ((((size_t)a.t_lds + 1) * kTmLanes * 2 + 15) & ~(size_t)15) +
                         (size_t)a.lev_stride * sizeof(int32_t);
   // (pass A's block-wide reductions take 256 bytes of static LDS)
@@ -667,16 +786,7 @@ static hipError_t launch_tm_passes(const CovTmArgs& a, int n_envs_sel, hipStream
     hipLaunchKernelGGL((cov_time_matrix_mw_kernel<V, true>), grid, dim3(kTmLanes * kTmWaves), lds_mw, s, a, a.sched);
     return hipGetLastError();
   }
-  for (const void* f : {reinterpret_cast<const void*>(&cov_time_matrix_kernel<V, false>),
-                        reinterpret_cast<const void*>(&cov_time_matrix_kernel<V, true>)}) {
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((cov_time_matrix_kernel<V, false>), grid, dim3(kTmLanes), lds, s, a, a.sched);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((cov_time_matrix_kernel<V, true>), grid, dim3(kTmLanes), lds, s, a, a.sched);
-  return hipGetLastError();
+  return launch_tm_narrow<V, kTmLanes>(a, n_envs_sel, s);
 }
 
 hipError_t launch_cov_time_matrix(const CovTmArgs& a, int n_envs_sel, bool wide, hipStream_t s) {

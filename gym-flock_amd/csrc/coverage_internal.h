@@ -282,7 +282,8 @@ __device__ __forceinline__ unsigned long long uf_largest(int32_t* parent, int32_
 struct CovTmArgs {
   int R, M, Tmax, horizon;
   int kcap;                  // flag slots per chunk: horizon+1, or Tmax+1 when unbounded
-  int nchunk;                // (Tmax + 63) / 64
+  int tm_s;                  // sources per wave of the launch: 64, 32, 16 or 8
+  int nchunk;                // (Tmax + tm_s - 1) / tm_s
   int t_lds;                 // largest target count among the selected envs
   const int32_t* envs;       // selected envs (blockIdx.y)
   const int32_t* ntg;        // (B)
@@ -301,6 +302,8 @@ struct CovTmArgs {
   int sched_stride;
   int32_t* lev_off;          // (B,lev_stride) each level's first schedule slot, then nslots
   int lev_stride;
+  int32_t* sched_scratch;    // (n_envs_sel,scratch_stride) the schedule kernel's edges and levels when they
+  int scratch_stride;        //   exceed the LDS (4 * e_max + 2 words per selected env), or nullptr: in LDS
   // greedy lists (cov_greedy_list_kernel), when Tmax <= kGreedyListMaxT
   const uint8_t* wide;       // (B) which cost form holds the env's matrix
   const int32_t* nbr;        // (B,Tmax,4)
@@ -333,11 +336,15 @@ struct CovGreedyArgs {
   int gstride;
 };
 
-size_t cov_time_matrix_lds_bytes(int t_lds, bool wide);
-size_t cov_tm_schedule_lds_bytes(int t_lds, int e_max);
+// the LDS tile of S sources per wave, and the largest S of 64, 32, 16, 8 whose tile fits a
+// CU's 160 KB (0: none)
+size_t cov_time_matrix_lds_bytes(int t_lds, bool wide, int S);
+int cov_time_matrix_sources(int t_lds, bool wide);
+// global: the edges and levels in CovTmArgs::sched_scratch, only the columns' state in LDS
+size_t cov_tm_schedule_lds_bytes(int t_lds, int e_max, bool global);
 hipError_t launch_cov_tm_schedule(const CovTmArgs& a, int n_envs_sel, int e_max, hipStream_t s);
-// Pass A + pass B over the selected envs; wide = uint16 entries (else uint8, which sets
-// overflow[b] for envs it cannot bound).
+// Pass A + pass B over the selected envs with a.tm_s sources per wave; wide = uint16
+// entries (else uint8, which sets overflow[b] for envs it cannot bound).
 hipError_t launch_cov_time_matrix(const CovTmArgs& a, int n_envs_sel, bool wide, hipStream_t s);
 hipError_t launch_cov_greedy(const CovGreedyArgs& a, hipStream_t s);
 // the greedy lists of the selected envs (after their time matrices)
@@ -381,7 +388,7 @@ hipError_t launch_cov_map(const CovMapArgs& a, hipStream_t s);
 // CoverageARL-v0 / CoverageFull-v0 (coverage_arl.hip): the target pool of an occupancy
 // grid (make_map.py:234-271, coverage_arl.py:46-62), shared by every env of a handle, and
 // the per-reset subgraph sampler (coverage_arl.py:64-83).
-constexpr int kPoolCap = 4096;  // pool points before the component step (grid_slice10: 1714)
+constexpr int kPoolCap = 8192;  // pool points before the component step (grid_slice10: 1714; 5855 at perimeter_delta 12)
 struct CovPoolArgs {
   int n0, n1;                // grid (n0, n1) bytes, nonzero = occupied
   const uint8_t* grid;
@@ -469,6 +476,8 @@ hipError_t launch_cov_hidden_graphs(const CovHiddenArgs& a, const float* edges_i
                                     float* edges, int32_t* snd, int32_t* rcv, hipStream_t s);
 
 size_t cov_step_lds_bytes(int R, int M);
+// cov_seed_reset_kernel's LDS: the stream's key, the permutation, its draws and the flags
+size_t cov_seed_reset_lds_bytes(int Tmax);
 // Observation wire formats: the flat FlattenDictWrapper rows (B, (12 + nf) M + 1), nf
 // features per row of a.nodes, and the batched unpack_obs graph tuple (edges compacted at
 // off[b]).

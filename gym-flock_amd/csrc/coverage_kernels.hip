@@ -48,14 +48,17 @@ __device__ __forceinline__ double dist2d(double ax, double ay, double bx, double
 // The radius test (within_radius, coverage_internal.h) decides `0 < sqrt(dx*dx + dy*dy) <= r`
 // exactly as dist2d rounds it, from the squared distance.
 
-// Targets staged in LDS with a cell grid (GRID, when Tmax <= kGraphLdsTargets): cells of
+// Targets staged in LDS with a cell grid (GRID, when they fit: cov_graph_lds_bytes): cells of
 // side h = radius (1 + 2^-20) over the targets' bounding box, so every target within the
 // radius of a node lies in the 3 x 3 cells around it (the margin dwarfs the rounding of the
 // cell coordinates); a node's in-radius targets are kept as its 4 smallest indices, the
 // row-major scan order of the reference. Without the grid (too many cells, a non-finite
 // coordinate, or GRID off) every node scans every target.
-constexpr int kGraphLdsTargets = 4096;
 constexpr int kGraphCells = 4096;
+// GRID's dynamic LDS: the targets, the cells' runs, the targets by cell. It is taken while
+// this and the kernel's static arrays (under 2 KB) fit a CU's 160 KB: up to 7,270 targets.
+constexpr size_t kGraphLdsMax = 158 * 1024;
+constexpr size_t cov_graph_lds_bytes(int Tmax) { return (size_t)Tmax * 20 + (size_t)kGraphCells * 4; }
 
 template <bool GRID>
 __global__ __launch_bounds__(kCovThreads) void cov_graph_kernel(CovArgs a, const int32_t* envs, int n_envs_sel) {
@@ -1040,8 +1043,8 @@ size_t cov_step_lds_bytes(int R, int M) {
 }
 
 hipError_t launch_cov_graph(const CovArgs& a, const int32_t* envs, int n, hipStream_t s) {
-  if (a.Tmax <= kGraphLdsTargets) {
-    const size_t lds = (size_t)a.Tmax * 16 + (size_t)kGraphCells * 4 + (size_t)a.Tmax * 4;
+  if (cov_graph_lds_bytes(a.Tmax) <= kGraphLdsMax) {
+    const size_t lds = cov_graph_lds_bytes(a.Tmax);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cov_graph_kernel<true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -1052,9 +1055,14 @@ hipError_t launch_cov_graph(const CovArgs& a, const int32_t* envs, int n, hipStr
   return hipGetLastError();
 }
 
+size_t cov_seed_reset_lds_bytes(int Tmax) { return (size_t)kMtN * 4 + (size_t)Tmax * 9; }
+
 hipError_t launch_cov_seed_reset(const CovArgs& a, uint32_t seed0, double frac, int32_t* start, uint8_t* visited0,
                                  hipStream_t s) {
-  const size_t lds = (size_t)kMtN * 4 + (size_t)a.Tmax * 9;
+  const size_t lds = cov_seed_reset_lds_bytes(a.Tmax);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cov_seed_reset_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(cov_seed_reset_kernel, dim3(a.B), dim3(64), lds, s, a, seed0, frac, start, visited0);
   return hipGetLastError();
 }

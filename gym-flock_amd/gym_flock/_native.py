@@ -120,6 +120,7 @@ COV_MAP_SEED = 0x1
 COV_MAP_CITIES = 0x2
 COV_MAP_DRAWS = 0x4
 COV_MAP_NO_WINDOW = 0x10
+COV_POOL_CAP = 8192  # pool points, and the most targets per map every Coverage path holds
 COV_MAP_NEAR_DEGENERATE = 0x1
 COV_MAP_TOO_MANY = 0x2
 COV_MAP_TOO_FEW = 0x4
@@ -241,6 +242,7 @@ SIGNATURES = {
     "cov_get_n_motion": [_P, _P],
     "cov_sync": [_P],
     "cov_set_streams": [_P, _I],
+    "cov_set_tm_plan": [_P, _I, _I],
     "cov_controller_greedy": [_P, _P, _P, _P],
     "cov_get_time_matrix": [_P, _I, _P, _P],
     "cov_get_actions": [_P, _P, _P],
@@ -1172,6 +1174,13 @@ class CoverageHandle:
         over two HIP streams and launches every other step once; 2 splits every step; 1
         keeps every step on the handle's stream."""
         check(self.lib.cov_set_streams(self.h, int(n)))
+
+    def set_tm_plan(self, sources_per_wave=0, schedule_in_global=False):
+        """How the next time matrices are built (cov_set_tm_plan): sources per wave (0: the
+        largest of 64, 32, 16, 8 whose LDS tile holds the map; else that value at most) and
+        whether the edge schedule's working arrays live in device memory. Every plan gives
+        the same matrices; every env's matrix is rebuilt at the next greedy call."""
+        check(self.lib.cov_set_tm_plan(self.h, int(sources_per_wave), 1 if schedule_in_global else 0))
 
     def controller_greedy(self, fetch=True):
         """Greedy expert actions (B,R) int32 and the (B,R) bool mask of robots the

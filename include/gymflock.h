@@ -461,7 +461,12 @@ typedef struct cov_occupancy_config {
 } cov_occupancy_config;
 #define COV_MAP_DRAWS     0x4  /* cov_generate_submaps: the graph_start draws are given     */
 #define COV_MAP_NO_WINDOW 0x10 /* status bit: no try gave a component of min_targets points */
-#define COV_POOL_CAP      4096 /* pool points before the component step                     */
+#define COV_POOL_CAP      8192 /* pool points before the component step; also the most
+                                  targets per map (max_nodes - n_robots) every Coverage
+                                  path holds: pool, motion graph, seeded reset, time matrix,
+                                  greedy controller, hidden-node observation. The fused
+                                  expert forms (COV_ACTIONS_GREEDY, cov_step_expert,
+                                  COV_NEXT_GREEDY) keep their own limit of 1024. */
 /* The target pool of grid (n0, n1) bytes, nonzero = occupied, on the device (one launch).
  * *n_pool_out (may be NULL) receives the pool's size. GF_EINVAL, before any launch, for a
  * grid without an occupied cell or one that may give more than COV_POOL_CAP points. */
@@ -494,7 +499,9 @@ int cov_reset(cov_handle* h, const int32_t* start, const uint8_t* visited);
  * replace=False) for the start targets and choice(arange(T) + R, int(T * frac_active),
  * replace=False) for the unvisited ones, bit-exact; the envs' streams then continue on the
  * device for COV_GREEDY_RNG (as after cov_set_rng). start_out (B,R) and visited_out
- * (B, max_nodes - R) may be NULL; otherwise they receive the draws, in cov_reset's layout. */
+ * (B, max_nodes - R) may be NULL; otherwise they receive the draws, in cov_reset's layout.
+ * GF_EINVAL where the draws' LDS (2496 + 9 * (max_nodes - R) bytes) exceeds a CU's 160 KB
+ * (above 17,927 targets: draw on the host, cov_reset). */
 int cov_reset_seeded(cov_handle* h, uint64_t seed, double frac_active, int32_t* start_out, uint8_t* visited_out);
 /* step(action) (:174-204, :234-364): actions[B][R] in [0,4). */
 int cov_step(cov_handle* h, const int32_t* actions, int flags);
@@ -548,6 +555,17 @@ int cov_get_n_motion(cov_handle* h, int32_t* n_motion);
  * handle's stream after both. */
 int cov_sync(cov_handle* h);
 int cov_set_streams(cov_handle* h, int n);
+/* How the time matrix is built (diagnostics and tests; the default chooses by size). One
+ * wave keeps the rows of sources_per_wave sources in LDS, (n_targets + 1) * sources_per_wave
+ * entries of one byte, or of two where a hop count passes 254: 0 takes the largest of 64,
+ * 32, 16, 8 that fits a CU's 160 KB for the largest map of a build (64 up to 2,559 targets,
+ * 16 and 8 at 8,192), another value caps it (GF_EINVAL unless 8, 16, 32 or 64, or if one
+ * byte per entry of max_nodes - n_robots + 1 targets does not fit; the two-byte rerun
+ * narrows the tile by itself where it must). schedule_in_global = 1 keeps the edge
+ * schedule's working arrays in device memory, as maps whose (2 n_targets + 4 n_edges + 4)
+ * words exceed the LDS do anyway. Every choice gives the same matrices. Takes effect at the
+ * next build and marks every env's matrix stale. */
+int cov_set_tm_plan(cov_handle* h, int sources_per_wave, int schedule_in_global);
 /* Greedy expert, controller(greedy=True) :800-872. On first use after cov_set_targets
  * it builds each env's time matrix (construct_time_matrix :621-653) on the device;
  * then every robot heads for its nearest unvisited target via the predecessor matrix.
@@ -555,7 +573,8 @@ int cov_set_streams(cov_handle* h, int n);
  * reference hands to np_random.choice(4) (target out of reach, :839-844 and :863-864)
  * get action 0 and needs_random = 1: draw those on the host in robot order and upload
  * the patched array with cov_set_actions. actions[B][R], needs_random[B][R] and
- * n_random may be NULL; with all three NULL the call does not synchronise. */
+ * n_random may be NULL; with all three NULL the call does not synchronise. Maps of up to
+ * COV_POOL_CAP targets; GF_EINVAL above. */
 int cov_controller_greedy(cov_handle* h, int32_t* actions, uint8_t* needs_random, int64_t* n_random);
 /* The resident actions (B,R) (the last cov_set_actions, cov_controller_greedy or
  * COV_ACTIONS_GREEDY step) and the needs_random flags (B,R) of the last greedy call;
