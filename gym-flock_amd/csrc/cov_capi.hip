@@ -120,6 +120,20 @@ struct cov_handle {
   uint8_t* gmask = nullptr;       // (B,Tmax) visited | !discovered
   int32_t* ngmask = nullptr;      // (B)
   int32_t* hnkeep = nullptr;      // (B) hsenders slots that are not -1
+  // cov_reset_device (allocated on first use): the selected envs, the same with the envs
+  // that are not reset struck out (-1), each env's start region, status bits and region size
+  int32_t* rs_envs = nullptr;     // (B)
+  int32_t* rs_ok = nullptr;       // (B)
+  uint8_t* rs_region = nullptr;   // (B,Tmax)
+  int32_t* rs_status = nullptr;   // (B)
+  int32_t* rs_nregion = nullptr;  // (B)
+  int32_t* rs_start_c = nullptr;  // (B,R) the selected envs' rows by position in the list
+  uint8_t* rs_visited_c = nullptr;  // (B,Tmax)
+  uint8_t* rs_region_c = nullptr;   // (B,Tmax)
+  // the configuration of the last cov_generate_maps call that drew its cities from the map
+  // streams (COV_RESET_NEW_MAPS draws the next maps with it)
+  cov_map_config map_cfg{};
+  bool map_cfg_set = false;
 };
 
 namespace {
@@ -156,7 +170,9 @@ void cov_release(cov_handle* h) {
                   h->goff, h->mt_key, h->mt_pos, h->map_key, h->map_pos, h->map_cities, h->map_nraw,
                   h->map_status, h->lat, h->lat_cell, h->lat_grid, h->occ_grid, h->pool_cellmap, h->pool_rawcell,
                   h->pool_raw, h->pool_xy, h->pool_cell, h->pool_info, h->pool_counts, h->sub_tries,
-                  h->discovered, h->hnodes, h->hsenders, h->gmask, h->ngmask, h->hnkeep};
+                  h->discovered, h->hnodes, h->hsenders, h->gmask, h->ngmask, h->hnkeep,
+                  h->rs_envs, h->rs_ok, h->rs_region, h->rs_status, h->rs_nregion,
+                  h->rs_start_c, h->rs_visited_c, h->rs_region_c};
   for (void* p : bufs)
     if (p) hipFree(p);
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
@@ -630,21 +646,28 @@ int cov_map_lattice(const cov_map_config* mc, double* xy, int32_t* n) {
   return GF_OK;
 }
 
-int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t map_seed, const double* cities,
-                      int flags, int32_t* n_targets_out, int32_t* status_out, double* cities_out) {
-  if (!h) return fail(GF_EINVAL, "null handle");
+}  // extern "C"
+
+namespace {
+
+// cov_generate_maps for the envs of `sel` (ascending; given cities and cities_out are rows
+// of a contiguous range starting at sel[0]): one launch of each kernel over the selection.
+// The outputs are indexed by position in sel.
+int generate_maps_sel(cov_handle* h, const cov_map_config* mc, const std::vector<int32_t>& sel, uint64_t map_seed,
+                      const double* cities, int flags, int32_t* n_targets_out, int32_t* status_out,
+                      double* cities_out) {
   if (int rc = check_map_config(mc)) return rc;
   if (flags & ~(COV_MAP_SEED | COV_MAP_CITIES)) return fail(GF_EINVAL, "flags: COV_MAP_SEED | COV_MAP_CITIES");
   const bool given = flags & COV_MAP_CITIES;
   if (given && !cities) return fail(GF_EINVAL, "COV_MAP_CITIES needs the cities");
   const int B = h->cfg.n_envs, NC = mc->n_cities;
-  if (env >= B) return fail(GF_EINVAL, "env index out of range");
+  const int nsel = (int)sel.size(), b0 = sel.empty() ? 0 : sel[0];
   if (!given && (flags & COV_MAP_SEED) && map_seed + (uint64_t)B > 0x100000000ull)
     return fail(GF_EINVAL, "map_seed + n_envs must fit in 32 bits (np.random.seed)");
   if (!given && !(flags & COV_MAP_SEED) && !h->map_seeded)
     return fail(GF_ESTATE, "the envs' map streams were never seeded (COV_MAP_SEED)");
   if (given)
-    for (size_t q = 0, nq = (size_t)(env < 0 ? B : 1) * NC * 2; q < nq; ++q)
+    for (size_t q = 0, nq = (size_t)nsel * NC * 2; q < nq; ++q)
       if (!std::isfinite(cities[q])) return fail(GF_EINVAL, "map: the given cities hold a NaN or an infinity");
   if (int rc = use(h)) return rc;
   int rc;
@@ -671,9 +694,6 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
   const double wfit_g = G > 0 ? ((double)lds_max - (double)lds_lat - 4.0 * G * G) / 20.0 : 0.0;
   if (wfit_g < wcap_scan) G = 0;  // the grid would cost waypoint capacity
   const int wcap = static_cast<int>(wcap_scan);
-  const int b0 = env < 0 ? 0 : env, b1 = env < 0 ? B : env + 1, nsel = b1 - b0;
-  std::vector<int32_t> sel;
-  for (int b = b0; b < b1; ++b) sel.push_back(b);
   GF_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, h->stream));
   gf::CovMapArgs m{};
   m.n_sel = nsel;
@@ -715,15 +735,17 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
     e = gf::launch_cov_map_cities(m, h->stream);
     if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_map_cities_kernel: ") + hipGetErrorString(e));
     if (flags & COV_MAP_SEED) h->map_seeded = true;
+    h->map_cfg = *mc;
+    h->map_cfg_set = true;
   }
   e = gf::launch_cov_map(m, h->stream);
   if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_map_kernel: ") + hipGetErrorString(e));
   e = gf::launch_cov_graph(h->a, h->envsel, nsel, h->stream);
   if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
   if (int rc3 = hidden_reset(h, h->envsel, nsel)) return rc3;
-  std::vector<int32_t> nraw(nsel), st(nsel), ntg(B);
-  GF_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
-  GF_HIP(hipMemcpyAsync(st.data(), h->map_status + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  std::vector<int32_t> nraw(B), st(B), ntg(B);
+  GF_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw, B * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(st.data(), h->map_status, B * 4, hipMemcpyDeviceToHost, h->stream));
   GF_HIP(hipMemcpyAsync(ntg.data(), h->ntg, B * 4, hipMemcpyDeviceToHost, h->stream));
   if (cities_out)
     GF_HIP(hipMemcpy2DAsync(cities_out, (size_t)NC * 16, h->map_cities + (size_t)b0 * gf::kMapMaxCities * 2,
@@ -732,18 +754,18 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
   GF_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
   std::string bad;
   for (int k = 0; k < nsel; ++k) {
-    const int b = b0 + k;
+    const int b = sel[k];
     h->ntg_host[b] = ntg[b];
     h->tm_valid[b] = 0;
-    if (n_targets_out) n_targets_out[k] = nraw[k];
-    if (status_out) status_out[k] = st[k];
-    if (bad.empty() && (st[k] & (gf::kMapTooMany | gf::kMapTooFew | gf::kMapOverflow))) {
+    if (n_targets_out) n_targets_out[k] = nraw[b];
+    if (status_out) status_out[k] = st[b];
+    if (bad.empty() && (st[b] & (gf::kMapTooMany | gf::kMapTooFew | gf::kMapOverflow))) {
       bad = "env " + std::to_string(b) + ": ";
-      if (st[k] & gf::kMapTooMany)
-        bad += "the map has " + std::to_string(nraw[k]) + " targets, more than max_nodes - n_robots = " +
+      if (st[b] & gf::kMapTooMany)
+        bad += "the map has " + std::to_string(nraw[b]) + " targets, more than max_nodes - n_robots = " +
                std::to_string(h->a.Tmax) + " (the reference's padded observation cannot hold them)";
-      else if (st[k] & gf::kMapTooFew)
-        bad += "the map has " + std::to_string(nraw[k]) + " targets, fewer than the robots";
+      else if (st[b] & gf::kMapTooFew)
+        bad += "the map has " + std::to_string(nraw[b]) + " targets, fewer than the robots";
       else
         bad += "more road waypoints than the map kernel holds";
     }
@@ -753,6 +775,28 @@ int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t
   for (int b = 0; b < B; ++b) h->has_graph = h->has_graph && h->ntg_host[b] > 0;
   if (!bad.empty()) return fail(GF_EINVAL, "cov_generate_maps: " + bad);
   return GF_OK;
+}
+
+// env < 0: every env; else that env
+std::vector<int32_t> env_range(const cov_handle* h, int env) {
+  std::vector<int32_t> sel;
+  const int B = h->cfg.n_envs;
+  for (int b = env < 0 ? 0 : env; b < (env < 0 ? B : env + 1); ++b) sel.push_back(b);
+  return sel;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cov_generate_maps(cov_handle* h, const cov_map_config* mc, int env, uint64_t map_seed, const double* cities,
+                      int flags, int32_t* n_targets_out, int32_t* status_out, double* cities_out) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (int rc = check_map_config(mc)) return rc;
+  if (flags & ~(COV_MAP_SEED | COV_MAP_CITIES)) return fail(GF_EINVAL, "flags: COV_MAP_SEED | COV_MAP_CITIES");
+  if ((flags & COV_MAP_CITIES) && !cities) return fail(GF_EINVAL, "COV_MAP_CITIES needs the cities");
+  if (env >= h->cfg.n_envs) return fail(GF_EINVAL, "env index out of range");
+  return generate_maps_sel(h, mc, env_range(h, env), map_seed, cities, flags, n_targets_out, status_out, cities_out);
 }
 
 int cov_get_targets(cov_handle* h, int env, double* targets) {
@@ -868,16 +912,20 @@ int cov_get_pool(cov_handle* h, double* targets, double* min_xy, double* max_xy,
   return GF_OK;
 }
 
-int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double* draws, int n_draws, int flags,
-                         int32_t* n_targets_out, int32_t* status_out, int32_t* tries_out) {
-  if (!h) return fail(GF_EINVAL, "null handle");
+}  // extern "C"
+
+namespace {
+
+// cov_generate_submaps for the envs of `sel` (ascending; outputs and given draws indexed by
+// position in sel): one launch of the sampler over the selection.
+int generate_submaps_sel(cov_handle* h, const std::vector<int32_t>& sel, uint64_t map_seed, const double* draws,
+                         int n_draws, int flags, int32_t* n_targets_out, int32_t* status_out, int32_t* tries_out) {
   if (flags & ~(COV_MAP_SEED | COV_MAP_DRAWS)) return fail(GF_EINVAL, "flags: COV_MAP_SEED | COV_MAP_DRAWS");
   const bool given = flags & COV_MAP_DRAWS;
   if (given && !draws) return fail(GF_EINVAL, "COV_MAP_DRAWS needs the draws");
   if (given && n_draws < 1) return fail(GF_EINVAL, "COV_MAP_DRAWS needs n_draws >= 1");
   if (given && n_draws > (1 << 20)) return fail(GF_EINVAL, "n_draws too large");
-  const int B = h->cfg.n_envs;
-  if (env >= B) return fail(GF_EINVAL, "env index out of range");
+  const int B = h->cfg.n_envs, nsel = (int)sel.size();
   if (!h->pool_loaded) return fail(GF_ESTATE, "no target pool (cov_load_occupancy)");
   if (!(h->occ.num_subgraphs > 1.0))
     return fail(GF_EINVAL, "num_subgraphs <= 1 is not sampled: the map is the whole pool (cov_set_targets)");
@@ -888,9 +936,6 @@ int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double
   if (gf::cov_submap_lds_bytes(h->pool_n) > 150 * 1024) return fail(GF_EINVAL, "the pool is too large for the sampler's LDS");
   if (int rc = use(h)) return rc;
   if (int rc = ensure_map_buffers(h)) return rc;
-  const int b0 = env < 0 ? 0 : env, b1 = env < 0 ? B : env + 1, nsel = b1 - b0;
-  std::vector<int32_t> sel;
-  for (int b = b0; b < b1; ++b) sel.push_back(b);
   GF_HIP(hipMemcpyAsync(h->envsel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, h->stream));
   const double* info = h->pool_info_host;
   gf::CovSubmapArgs m{};
@@ -939,28 +984,28 @@ int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double
   e = gf::launch_cov_graph(h->a, h->envsel, nsel, h->stream);
   if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_graph_kernel: ") + hipGetErrorString(e));
   if (int rc3 = hidden_reset(h, h->envsel, nsel)) return rc3;
-  std::vector<int32_t> nraw(nsel), st(nsel), tr(nsel), ntg(B);
-  GF_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
-  GF_HIP(hipMemcpyAsync(st.data(), h->map_status + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
-  GF_HIP(hipMemcpyAsync(tr.data(), h->sub_tries + b0, nsel * 4, hipMemcpyDeviceToHost, h->stream));
+  std::vector<int32_t> nraw(B), st(B), tr(B), ntg(B);
+  GF_HIP(hipMemcpyAsync(nraw.data(), h->map_nraw, B * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(st.data(), h->map_status, B * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(tr.data(), h->sub_tries, B * 4, hipMemcpyDeviceToHost, h->stream));
   GF_HIP(hipMemcpyAsync(ntg.data(), h->ntg, B * 4, hipMemcpyDeviceToHost, h->stream));
   if (int rc2 = check_err(h)) return rc2;  // synchronises; motion-graph errors (degree > 4, edges)
   GF_HIP(hipMemcpy(h->n_motion_host.data(), h->a.n_motion, B * sizeof(int32_t), hipMemcpyDeviceToHost));
   std::string bad;
   for (int k = 0; k < nsel; ++k) {
-    const int b = b0 + k;
+    const int b = sel[k];
     h->ntg_host[b] = ntg[b];
     h->tm_valid[b] = 0;
-    if (n_targets_out) n_targets_out[k] = nraw[k];
-    if (status_out) status_out[k] = st[k];
-    if (tries_out) tries_out[k] = tr[k];
+    if (n_targets_out) n_targets_out[k] = nraw[b];
+    if (status_out) status_out[k] = st[b];
+    if (tries_out) tries_out[k] = tr[b];
     if (!bad.empty()) continue;
-    if (st[k] & gf::kMapTooMany)
-      bad = "env " + std::to_string(b) + ": the map has " + std::to_string(nraw[k]) +
+    if (st[b] & gf::kMapTooMany)
+      bad = "env " + std::to_string(b) + ": the map has " + std::to_string(nraw[b]) +
             " targets, more than max_nodes - n_robots = " + std::to_string(h->a.Tmax);
-    else if (st[k] & gf::kMapTooFew)
-      bad = "env " + std::to_string(b) + ": the map has " + std::to_string(nraw[k]) + " targets, fewer than the robots";
-    else if ((st[k] & gf::kMapNoWindow) && !given)
+    else if (st[b] & gf::kMapTooFew)
+      bad = "env " + std::to_string(b) + ": the map has " + std::to_string(nraw[b]) + " targets, fewer than the robots";
+    else if ((st[b] & gf::kMapNoWindow) && !given)
       bad = "env " + std::to_string(b) + ": no window with a component of " + std::to_string(h->occ.min_targets) +
             " targets in max_tries = " + std::to_string(h->occ.max_tries) + " tries";
   }
@@ -969,6 +1014,22 @@ int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double
   for (int b = 0; b < B; ++b) h->has_graph = h->has_graph && h->ntg_host[b] > 0;
   if (!bad.empty()) return fail(GF_EINVAL, "cov_generate_submaps: " + bad);
   return GF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cov_generate_submaps(cov_handle* h, int env, uint64_t map_seed, const double* draws, int n_draws, int flags,
+                         int32_t* n_targets_out, int32_t* status_out, int32_t* tries_out) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (flags & ~(COV_MAP_SEED | COV_MAP_DRAWS)) return fail(GF_EINVAL, "flags: COV_MAP_SEED | COV_MAP_DRAWS");
+  if ((flags & COV_MAP_DRAWS) && !draws) return fail(GF_EINVAL, "COV_MAP_DRAWS needs the draws");
+  if ((flags & COV_MAP_DRAWS) && n_draws < 1) return fail(GF_EINVAL, "COV_MAP_DRAWS needs n_draws >= 1");
+  if ((flags & COV_MAP_DRAWS) && n_draws > (1 << 20)) return fail(GF_EINVAL, "n_draws too large");
+  if (env >= h->cfg.n_envs) return fail(GF_EINVAL, "env index out of range");
+  return generate_submaps_sel(h, env_range(h, env), map_seed, draws, n_draws, flags, n_targets_out, status_out,
+                              tries_out);
 }
 
 int cov_reset(cov_handle* h, const int32_t* start, const uint8_t* visited) {
@@ -1023,6 +1084,141 @@ int cov_reset_seeded(cov_handle* h, uint64_t seed, double frac_active, int32_t* 
   if (visited_out) GF_HIP(hipMemcpyAsync(visited_out, h->visited0, B * Tm, hipMemcpyDeviceToHost, h->stream));
   GF_HIP(hipStreamSynchronize(h->stream));
   h->has_state = true;
+  return GF_OK;
+}
+
+static_assert(COV_RESET_REGION_SHORT == gf::kResetRegionShort && COV_RESET_REGION_SMALL == gf::kResetRegionSmall,
+              "gymflock.h and coverage_internal.h disagree");
+
+int cov_reset_device(cov_handle* h, const cov_reset_config* rc, const uint8_t* env_mask, int32_t* start_out,
+                     uint8_t* visited_out, uint8_t* region_out, int32_t* status_out, int32_t* n_reset_out) {
+  if (!h || !rc) return fail(GF_EINVAL, "null argument");
+  const size_t B = h->cfg.n_envs, R = h->cfg.n_robots, Tm = h->a.Tmax;
+  if (!(rc->frac_active >= 0.0 && rc->frac_active <= 1.0)) return fail(GF_EINVAL, "frac_active must be in [0, 1]");
+  if (rc->nearby < 0) return fail(GF_EINVAL, "nearby must be >= 0");
+  if (rc->flags & ~(COV_RESET_SEED | COV_RESET_NEW_MAPS | COV_RESET_DONE))
+    return fail(GF_EINVAL, "flags: COV_RESET_SEED | COV_RESET_NEW_MAPS | COV_RESET_DONE");
+  if (R > (size_t)gf::kMtN) return fail(GF_EINVAL, "device np_random draws need n_robots <= 624");
+  if (gf::cov_reset_draw_lds_bytes((int)Tm) > 160 * 1024)  // key, permutation, draws, two bit sets, flags
+    return fail(GF_EINVAL, "max_nodes - n_robots too large for the device reset draws (draw on the host)");
+  const bool seeded = rc->flags & COV_RESET_SEED, new_maps = rc->flags & COV_RESET_NEW_MAPS;
+  if (seeded && rc->seed + B > 0x100000000ull)
+    return fail(GF_EINVAL, "seed + n_envs must fit in 32 bits (RandomState seeds)");
+  if (n_reset_out) *n_reset_out = 0;
+  if (!h->has_graph && !new_maps) return fail(GF_ESTATE, "set the target graph of every env first (cov_set_targets)");
+  if (!seeded && !h->mt_key)
+    return fail(GF_ESTATE, "no np_random streams on the device (cov_set_rng, cov_reset_seeded or COV_RESET_SEED)");
+  const bool by_done = !env_mask && (rc->flags & COV_RESET_DONE);
+  if (by_done && !h->has_state) return fail(GF_ESTATE, "COV_RESET_DONE: reset first (no done flags yet)");
+  const bool sampled = h->pool_loaded && h->occ.num_subgraphs > 1.0;
+  if (new_maps && !sampled && !h->map_cfg_set)
+    return fail(GF_ESTATE, "COV_RESET_NEW_MAPS: no maps were drawn from the map streams yet (cov_generate_maps / "
+                           "cov_generate_submaps)");
+  if (int rc0 = use(h)) return rc0;
+  std::vector<int32_t> sel;
+  if (by_done) {
+    std::vector<uint8_t> done(B);
+    GF_HIP(hipMemcpyAsync(done.data(), h->a.done, B, hipMemcpyDeviceToHost, h->stream));
+    GF_HIP(hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < B; ++b)
+      if (done[b]) sel.push_back((int32_t)b);
+  } else {
+    for (size_t b = 0; b < B; ++b)
+      if (!env_mask || env_mask[b]) sel.push_back((int32_t)b);
+  }
+  const int nsel = (int)sel.size();
+  if (nsel == 0) return GF_OK;
+  if (!h->has_state && (size_t)nsel != B)
+    return fail(GF_ESTATE, "the first reset must take every env (the others have no state yet)");
+  if (new_maps) {  // the selected envs' next maps, from their own map streams
+    const int rcm = sampled ? generate_submaps_sel(h, sel, 0, nullptr, 0, 0, nullptr, nullptr, nullptr)
+                            : generate_maps_sel(h, &h->map_cfg, sel, 0, nullptr, 0, nullptr, nullptr, nullptr);
+    if (rcm) return rcm;
+  }
+  if (!h->has_graph) return fail(GF_ESTATE, "set the target graph of every env first (cov_set_targets)");
+  int rca;
+  if (!h->mt_key && ((rca = dalloc_zero(&h->mt_key, B * gf::kMtN)) || (rca = dalloc_zero(&h->mt_pos, B)))) return rca;
+  if (!h->rs_envs &&
+      ((rca = dalloc_zero(&h->rs_envs, B)) || (rca = dalloc_zero(&h->rs_ok, B)) || (rca = dalloc_zero(&h->rs_region, B * Tm)) ||
+       (rca = dalloc_zero(&h->rs_status, B)) || (rca = dalloc_zero(&h->rs_nregion, B)) ||
+       (rca = dalloc_zero(&h->rs_start_c, B * R)) || (rca = dalloc_zero(&h->rs_visited_c, B * Tm)) ||
+       (rca = dalloc_zero(&h->rs_region_c, B * Tm))))
+    return rca;
+  // a part of the envs: their rows also by position in the list, one copy per array
+  const bool compact = (size_t)nsel != B;
+  GF_HIP(hipMemcpyAsync(h->rs_envs, sel.data(), (size_t)nsel * 4, hipMemcpyHostToDevice, h->stream));
+  gf::CovResetDrawArgs d{};
+  d.n_sel = nsel;
+  d.envs = h->rs_envs;
+  d.envs_ok = h->rs_ok;
+  d.R = (int)R;
+  d.Tmax = (int)Tm;
+  d.nearby = rc->nearby;
+  d.seed = seeded ? 1 : 0;
+  d.seed0 = static_cast<uint32_t>(rc->seed);
+  d.frac = rc->frac_active;
+  d.ntg = h->ntg;
+  d.nbr = h->a.nbr;
+  d.cnt = h->a.cnt;
+  d.mt_key = h->mt_key;
+  d.mt_pos = h->mt_pos;
+  d.start = h->start;
+  d.visited0 = h->visited0;
+  d.region = h->rs_region;
+  d.status = h->rs_status;
+  d.nregion = h->rs_nregion;
+  d.start_c = compact && start_out ? h->rs_start_c : nullptr;
+  d.visited_c = compact && visited_out ? h->rs_visited_c : nullptr;
+  d.region_c = compact && region_out ? h->rs_region_c : nullptr;
+  hipError_t e = gf::launch_cov_reset_draw(d, h->stream);
+  if (e == hipSuccess) e = gf::launch_cov_reset_list(h->a, h->start, h->visited0, h->rs_ok, nsel, h->stream);
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_reset_device: ") + hipGetErrorString(e));
+  if (int rc1 = hidden_reset(h, h->rs_ok, nsel)) return rc1;
+  gf::CovArgs a = h->a;
+  a.actions = nullptr;
+  e = gf::launch_cov_step_list(a, h->rs_ok, nsel, h->stream);
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_step_list_kernel: ") + hipGetErrorString(e));
+  if (h->hidden) {
+    e = gf::launch_cov_hidden_list(hidden_args(h), h->rs_ok, nsel, h->stream);
+    if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_hidden_list_kernel: ") + hipGetErrorString(e));
+  }
+  // the selected envs' rows only (a struck env's start row reads -1, its visited row 1)
+  std::vector<int32_t> st(B, 0), nreg(B, 0), start_h;
+  std::vector<uint8_t> visited_h, region_h;
+  GF_HIP(hipMemcpyAsync(st.data(), h->rs_status, B * 4, hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(nreg.data(), h->rs_nregion, B * 4, hipMemcpyDeviceToHost, h->stream));
+  if (!compact) {
+    if (int rc2 = copy_out(h, start_out, h->start, B * R * 4)) return rc2;
+    if (int rc2 = copy_out(h, visited_out, h->visited0, B * Tm)) return rc2;
+    if (int rc2 = copy_out(h, region_out, h->rs_region, B * Tm)) return rc2;
+  } else {
+    if (start_out) start_h.resize((size_t)nsel * R);
+    if (visited_out) visited_h.resize((size_t)nsel * Tm);
+    if (region_out) region_h.resize((size_t)nsel * Tm);
+    if (int rc2 = copy_out(h, start_out ? start_h.data() : nullptr, h->rs_start_c, (size_t)nsel * R * 4)) return rc2;
+    if (int rc2 = copy_out(h, visited_out ? visited_h.data() : nullptr, h->rs_visited_c, (size_t)nsel * Tm)) return rc2;
+    if (int rc2 = copy_out(h, region_out ? region_h.data() : nullptr, h->rs_region_c, (size_t)nsel * Tm)) return rc2;
+  }
+  GF_HIP(hipStreamSynchronize(h->stream));
+  int small = -1, nsmall = 0;
+  for (int k = 0; k < nsel; ++k) {
+    const int32_t b = sel[k];
+    if (status_out) status_out[b] = st[b];
+    if (st[b] & gf::kResetRegionSmall) {
+      if (small < 0) small = b;
+      ++nsmall;
+    }
+    if (!compact) continue;
+    if (start_out) std::memcpy(start_out + b * R, start_h.data() + (size_t)k * R, R * 4);
+    if (visited_out) std::memcpy(visited_out + b * Tm, visited_h.data() + (size_t)k * Tm, Tm);
+    if (region_out) std::memcpy(region_out + b * Tm, region_h.data() + (size_t)k * Tm, Tm);
+  }
+  if (n_reset_out) *n_reset_out = nsel - nsmall;
+  if (nsmall == 0) h->has_state = true;
+  if (nsmall)
+    return fail(GF_EINVAL, "cov_reset_device: env " + std::to_string(small) + ": its start region has " +
+                               std::to_string(nreg[small]) + " nodes, fewer than the " + std::to_string(R) +
+                               " robots (numpy's choice raises); the env was not reset");
   return GF_OK;
 }
 
@@ -1449,6 +1645,12 @@ int cov_get_n_motion(cov_handle* h, int32_t* n_motion) {
   if (int rc = use(h)) return rc;
   if (int rc = copy_out(h, n_motion, h->a.n_motion, (size_t)h->cfg.n_envs * 4)) return rc;
   GF_HIP(hipStreamSynchronize(h->stream));
+  return GF_OK;
+}
+
+int cov_get_n_targets(cov_handle* h, int32_t* n_targets) {
+  if (!h || !n_targets) return fail(GF_EINVAL, "null argument");
+  for (int b = 0; b < h->cfg.n_envs; ++b) n_targets[b] = h->ntg_host[b];
   return GF_OK;
 }
 

@@ -31,10 +31,11 @@ constexpr int kHidThreads = 256;
 
 __device__ __forceinline__ uint32_t hid_bit(const uint32_t* bits, int k) { return (bits[k >> 5] >> (k & 31)) & 1u; }
 
-__global__ __launch_bounds__(kHidThreads) void cov_hidden_kernel(CovHiddenArgs a) {
+// The pass over env b (cov_hidden_kernel: the workgroup's index; cov_hidden_list_kernel: an
+// entry of a device list)
+__device__ __forceinline__ void cov_hidden_body(const CovHiddenArgs& a, const int b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hid_smem[];
   __shared__ int cnt_s[2];  // kept senders, masked targets
-  const int b = blockIdx.x;
   const int R = a.R, M = a.M, Tm = a.Tmax, E = 4 * M, W = (M + 31) >> 5;
   const int T = min(a.ntg[b], Tm);
   const int tid = threadIdx.x;
@@ -120,9 +121,20 @@ __global__ __launch_bounds__(kHidThreads) void cov_hidden_kernel(CovHiddenArgs a
   }
 }
 
+__global__ __launch_bounds__(kHidThreads) void cov_hidden_kernel(CovHiddenArgs a) { cov_hidden_body(a, blockIdx.x); }
+
+// cov_reset_device: the listed envs only (entries < 0 skipped). A kernel of its own, so the
+// pass after every step keeps its arguments.
+__global__ __launch_bounds__(kHidThreads) void cov_hidden_list_kernel(CovHiddenArgs a, const int32_t* envs) {
+  const int b = envs[blockIdx.x];
+  if (b < 0) return;
+  cov_hidden_body(a, b);
+}
+
 // discovered := robots only (reset(), a new graph) for the selected envs
 __global__ __launch_bounds__(kHidThreads) void cov_hidden_reset_kernel(CovHiddenArgs a, const int32_t* envs) {
   const int b = envs ? envs[blockIdx.x] : blockIdx.x;
+  if (b < 0) return;
   uint8_t* disc = a.discovered + (size_t)b * a.M;
   for (int k = threadIdx.x; k < a.M; k += kHidThreads) disc[k] = k < a.R ? 1 : 0;
 }
@@ -169,6 +181,11 @@ hipError_t launch_cov_hidden(const CovHiddenArgs& a, hipStream_t s) {
   void* args[] = {const_cast<CovHiddenArgs*>(&a)};
   return hipLaunchKernel(reinterpret_cast<const void*>(&cov_hidden_kernel), dim3(a.B), dim3(kHidThreads), args,
                          cov_hidden_lds_bytes(a.R, a.M), s);
+}
+
+hipError_t launch_cov_hidden_list(const CovHiddenArgs& a, const int32_t* envs, int n, hipStream_t s) {
+  hipLaunchKernelGGL(cov_hidden_list_kernel, dim3(n), dim3(kHidThreads), cov_hidden_lds_bytes(a.R, a.M), s, a, envs);
+  return hipGetLastError();
 }
 
 hipError_t launch_cov_hidden_reset(const CovHiddenArgs& a, const int32_t* envs, int n, hipStream_t s) {

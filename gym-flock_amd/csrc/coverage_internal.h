@@ -193,6 +193,52 @@ __device__ __forceinline__ void greedy_direct_list(const uint32_t* vbits, int T,
 // uniform p is randint(0, 4): one 32-bit output, masked to 2 bits (the mask equals the
 // range, so no draw is ever rejected).
 
+// RandomState.permutation(n) into perm[0, n) from the stream (key in LDS, pos wave-uniform),
+// by one wave (cov_seed_reset_kernel, cov_reset_draw_kernel). The draws do not depend on the
+// permutation, so they come first: 64 tempered words per round (one LDS load per lane),
+// consumed in stream order by a register chain (readlane; the masked rejection of each i),
+// the accepted ones into vseq[i]; then lane 0 runs the swaps, one LDS round trip each (the
+// draws and swaps interleaved waited on two per swap; profiles/r06/ab_seed_reset_draws.txt).
+// perm and vseq hold n words each. Every lane of the wave calls it.
+__device__ __forceinline__ void cov_permute(uint32_t* key, int& pos, int32_t* perm, int32_t* vseq, int n) {
+  const int lane = threadIdx.x;
+  for (int k = lane; k < n; k += 64) perm[k] = k;
+  int i = n - 1;  // wave-uniform
+  while (i >= 1) {
+    if (pos == kMtN) {
+      mt_regen<64>(key);
+      pos = 0;
+    }
+    const int avail = min(64, kMtN - pos);
+    const uint32_t wl = lane < avail ? mt_temper(key[pos + lane]) : 0u;
+    int u = 0;
+    for (; u < avail && i >= 1; ++u) {
+      const uint32_t mask = 0xFFFFFFFFu >> __builtin_clz(static_cast<uint32_t>(i));
+      const uint32_t v = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(wl), u)) & mask;
+      if (v <= static_cast<uint32_t>(i)) {
+        if (lane == 0) vseq[i] = static_cast<int>(v);
+        --i;
+      }
+    }
+    pos += u;
+  }
+  __syncthreads();
+  if (lane == 0 && n > 1) {  // one lane: its LDS reads and writes stay in program order
+    // the next swap's draw is read with this swap's entries (vseq is not written here),
+    // so a swap waits on one LDS round trip, not two
+    int v = vseq[n - 1];
+    for (int k = n - 1; k >= 1; --k) {
+      const int vnext = vseq[k - 1];  // vseq[0]: read, never used
+      const int t = perm[k];
+      const int pv = perm[v];
+      perm[k] = pv;
+      perm[v] = t;
+      v = vnext;
+    }
+  }
+  __syncthreads();
+}
+
 // Shared by the map kernels (coverage_maps.hip, coverage_arl.hip): workgroup compaction
 // and the largest connected component of a radius graph by union-find in LDS.
 //
@@ -469,7 +515,10 @@ struct CovHiddenArgs {
 };
 size_t cov_hidden_lds_bytes(int R, int M);
 hipError_t launch_cov_hidden(const CovHiddenArgs& a, hipStream_t s);
-// discovered := robots only, for the n envs listed (envs == nullptr: envs 0..n-1)
+// the same pass over the n envs listed on the device (an entry < 0 is skipped)
+hipError_t launch_cov_hidden_list(const CovHiddenArgs& a, const int32_t* envs, int n, hipStream_t s);
+// discovered := robots only, for the n envs listed (envs == nullptr: envs 0..n-1; an entry
+// < 0 is skipped)
 hipError_t launch_cov_hidden_reset(const CovHiddenArgs& a, const int32_t* envs, int n, hipStream_t s);
 // the unpack_obs tuple's edges of the hidden observation (kept slots compacted at off[b])
 hipError_t launch_cov_hidden_graphs(const CovHiddenArgs& a, const float* edges_in, const int64_t* off, bool mask_all,
@@ -486,6 +535,41 @@ hipError_t launch_cov_graphs(const CovArgs& a, const int64_t* off, bool mask_all
                              int32_t* rcv, hipStream_t s);
 hipError_t launch_cov_graph(const CovArgs& a, const int32_t* envs, int n, hipStream_t s);
 hipError_t launch_cov_reset(const CovArgs& a, const int32_t* start, const uint8_t* visited0, hipStream_t s);
+// Env-list forms for cov_reset_device (envs on the device, n entries; an entry < 0 is
+// skipped): the reset pass and the no-action observation pass of the listed envs only
+hipError_t launch_cov_reset_list(const CovArgs& a, const int32_t* start, const uint8_t* visited0, const int32_t* envs,
+                                 int n, hipStream_t s);
+hipError_t launch_cov_step_list(const CovArgs& a, const int32_t* envs, int n, hipStream_t s);
+
+// cov_reset_device's draws (coverage_reset.hip): one wave per listed env
+struct CovResetDrawArgs {
+  int n_sel;
+  const int32_t* envs;    // (n_sel) env of each wave
+  int32_t* envs_ok;       // (n_sel) out: the env, or -1 when it is not to be reset (kResetRegionSmall)
+  int R, Tmax;
+  int nearby;             // 0: every target may be a start; n > 0: get_n_nearest(choice(T), n)
+  int seed;               // 1: the stream of env b starts as RandomState(seed0 + b); 0: continues
+  uint32_t seed0;
+  double frac;
+  const int32_t* ntg;     // (B)
+  const int32_t* nbr;     // (B,Tmax,4)
+  const int32_t* cnt;     // (B,Tmax)
+  uint32_t* mt_key;       // (B,624)
+  int32_t* mt_pos;        // (B)
+  int32_t* start;         // (B,R) out
+  uint8_t* visited0;      // (B,Tmax) out
+  uint8_t* region;        // (B,Tmax) out: 1 for the targets of the start region
+  int32_t* status;        // (B) out: kResetRegionShort | kResetRegionSmall
+  int32_t* nregion;       // (B) out: region nodes
+  // the same rows by position in envs (n_sel rows each; any may be nullptr), so a few envs'
+  // outputs reach the host in one copy per array
+  int32_t* start_c;       // (n_sel,R)
+  uint8_t* visited_c;     // (n_sel,Tmax)
+  uint8_t* region_c;      // (n_sel,Tmax)
+};
+constexpr int32_t kResetRegionShort = 1, kResetRegionSmall = 2;
+size_t cov_reset_draw_lds_bytes(int Tmax);
+hipError_t launch_cov_reset_draw(const CovResetDrawArgs& a, hipStream_t s);
 // reset()'s random draws on the device for envs seeded seed0 + b (start (B,R), visited0
 // (B,Tmax)), the streams left in a.mt_key / a.mt_pos
 hipError_t launch_cov_seed_reset(const CovArgs& a, uint32_t seed0, double frac, int32_t* start, uint8_t* visited0,

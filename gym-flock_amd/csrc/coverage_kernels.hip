@@ -284,14 +284,14 @@ __device__ __forceinline__ int action_node(const int32_t* nbr, const int32_t* cn
 // After an external placement, a new graph or a reset, everything is recomputed.
 // UIN (cov_step_host): the env batch's actions arrive in the kernel arguments (CovArgsU)
 // instead of being read from memory, one dependent round trip fewer.
-// One step of env a.env0 + blockIdx.x (the kernels below): MULTI also records the step's
+// One step of env b (a.env0 + blockIdx.x in the kernels below, an entry of a device list in
+// cov_step_list_kernel): MULTI also records the step's
 // reward and done flag at [it][b] of reward_k / done_k.
 template <int NT, bool MULTI>
-__device__ __forceinline__ void cov_step_body(const CovArgs& a, [[maybe_unused]] int it,
+__device__ __forceinline__ void cov_step_body(const CovArgs& a, const int b, [[maybe_unused]] int it,
                                               [[maybe_unused]] double* reward_k, [[maybe_unused]] uint8_t* done_k) {
   constexpr int RPT = kCovThreads / NT;  // robots per thread when R <= kCovThreads
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int b = a.env0 + blockIdx.x;
   const int R = a.R, M = a.M, Tm = a.Tmax, E = 4 * M;
   const int T = a.ntg[b];
   int* cur_s = reinterpret_cast<int*>(smem);          // R: node before the move
@@ -816,7 +816,7 @@ __global__ __launch_bounds__(NT) void cov_step_kernel(typename std::conditional<
     if constexpr (UIN) return &uargs;
     else return &p;
   }();
-  cov_step_body<NT, false>(a, 0, nullptr, nullptr);
+  cov_step_body<NT, false>(a, a.env0 + blockIdx.x, 0, nullptr, nullptr);
 #ifdef GF_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   GF_COV_STAMP(4);
@@ -834,16 +834,27 @@ template <int NT>
 __global__ __launch_bounds__(NT) void cov_step_multi_kernel(CovArgsM p) {
   const int n = p.k_steps > 1 ? p.k_steps : 1;
   for (int it = 0; it < n; ++it) {
-    cov_step_body<NT, true>(p.a, it, p.reward_k, p.done_k);
+    cov_step_body<NT, true>(p.a, p.a.env0 + blockIdx.x, it, p.reward_k, p.done_k);
     __syncthreads();
   }
 }
 
+// cov_reset_device: the observation pass (a.actions == nullptr) of the envs of a device list,
+// entries < 0 skipped. A kernel of its own: the step's arguments and code stay as they are.
+template <int NT>
+__global__ __launch_bounds__(NT) void cov_step_list_kernel(CovArgs a, const int32_t* envs) {
+  const int b = envs[blockIdx.x];
+  if (b < 0) return;
+  cov_step_body<NT, false>(a, b, 0, nullptr, nullptr);
+}
+
 // reset (:405-424 after the random draws): robots onto their start targets, the
-// unvisited flags, then the same observation pass as a step without actions.
+// unvisited flags, then the same observation pass as a step without actions. envs: the env
+// of each workgroup (cov_reset_device; entries < 0 skipped), or nullptr: the workgroup's index.
 __global__ __launch_bounds__(kCovThreads) void cov_reset_kernel(CovArgs a, const int32_t* start,
-                                                                 const uint8_t* visited0) {
-  const int b = blockIdx.x;
+                                                                 const uint8_t* visited0, const int32_t* envs) {
+  const int b = envs ? envs[blockIdx.x] : blockIdx.x;
+  if (b < 0) return;
   const int R = a.R, M = a.M, Tm = a.Tmax;
   const int T = a.ntg[b];
   const double* tg = a.tgt + (size_t)b * Tm * 2;
@@ -901,48 +912,7 @@ __global__ __launch_bounds__(64) void cov_seed_reset_kernel(CovArgs a, uint32_t 
   }
   __syncthreads();
   int pos = kMtN;  // wave-uniform
-  // RandomState.permutation(n) into perm[0, n). The draws do not depend on the permutation,
-  // so they come first: 64 tempered words per round (one LDS load per lane), consumed in
-  // stream order by a register chain (readlane; the masked rejection of each i), the
-  // accepted ones into vseq[i]; then lane 0 runs the swaps, one LDS round trip each (the
-  // draws and swaps interleaved waited on two per swap; profiles/r06/ab_seed_reset_draws.txt)
-  auto permute = [&](int n) {
-    for (int k = lane; k < n; k += 64) perm[k] = k;
-    int i = n - 1;  // wave-uniform
-    while (i >= 1) {
-      if (pos == kMtN) {
-        mt_regen<64>(key);
-        pos = 0;
-      }
-      const int avail = min(64, kMtN - pos);
-      const uint32_t wl = lane < avail ? mt_temper(key[pos + lane]) : 0u;
-      int u = 0;
-      for (; u < avail && i >= 1; ++u) {
-        const uint32_t mask = 0xFFFFFFFFu >> __builtin_clz(static_cast<uint32_t>(i));
-        const uint32_t v = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(wl), u)) & mask;
-        if (v <= static_cast<uint32_t>(i)) {
-          if (lane == 0) vseq[i] = static_cast<int>(v);
-          --i;
-        }
-      }
-      pos += u;
-    }
-    __syncthreads();
-    if (lane == 0 && n > 1) {  // one lane: its LDS reads and writes stay in program order
-      // the next swap's draw is read with this swap's entries (vseq is not written here),
-      // so a swap waits on one LDS round trip, not two
-      int v = vseq[n - 1];
-      for (int k = n - 1; k >= 1; --k) {
-        const int vnext = vseq[k - 1];  // vseq[0]: read, never used
-        const int t = perm[k];
-        const int pv = perm[v];
-        perm[k] = pv;
-        perm[v] = t;
-        v = vnext;
-      }
-    }
-    __syncthreads();
-  };
+  auto permute = [&](int n) { cov_permute(key, pos, perm, vseq, n); };
   permute(T);
   for (int k = lane; k < R; k += 64) start[(size_t)b * R + k] = perm[k];
   __syncthreads();
@@ -1068,7 +1038,20 @@ hipError_t launch_cov_seed_reset(const CovArgs& a, uint32_t seed0, double frac, 
 }
 
 hipError_t launch_cov_reset(const CovArgs& a, const int32_t* start, const uint8_t* visited0, hipStream_t s) {
-  hipLaunchKernelGGL(cov_reset_kernel, dim3(a.B), dim3(kCovThreads), 0, s, a, start, visited0);
+  hipLaunchKernelGGL(cov_reset_kernel, dim3(a.B), dim3(kCovThreads), 0, s, a, start, visited0,
+                     static_cast<const int32_t*>(nullptr));
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_reset_list(const CovArgs& a, const int32_t* start, const uint8_t* visited0, const int32_t* envs,
+                                 int n, hipStream_t s) {
+  hipLaunchKernelGGL(cov_reset_kernel, dim3(n), dim3(kCovThreads), 0, s, a, start, visited0, envs);
+  return hipGetLastError();
+}
+
+hipError_t launch_cov_step_list(const CovArgs& a, const int32_t* envs, int n, hipStream_t s) {
+  hipLaunchKernelGGL(cov_step_list_kernel<kCovThreads>, dim3(n), dim3(kCovThreads), cov_step_lds_bytes(a.R, a.M), s, a,
+                     envs);
   return hipGetLastError();
 }
 

@@ -37,7 +37,18 @@ if HAVE_GYM:  # pragma: no cover - gym is not installed in the build image
 
 
 def make(env_id, **kwargs):
-    """gym.make() equivalent that works without gym (no TimeLimit wrapper)."""
+    """gym.make() equivalent that works without gym (no TimeLimit wrapper). reset_mode= is
+    passed to the constructor where it takes it; an env whose constructor keeps the
+    reference's signature (ExploreEnv) gets it through set_reset_mode() instead."""
     import importlib
+    import inspect
     mod, cls = ENV_IDS[env_id][0].split(":")
-    return getattr(importlib.import_module(mod), cls)(**kwargs)
+    env_cls = getattr(importlib.import_module(mod), cls)
+    late = None
+    if "reset_mode" in kwargs and "reset_mode" not in inspect.signature(env_cls.__init__).parameters \
+            and hasattr(env_cls, "set_reset_mode"):
+        late = kwargs.pop("reset_mode")
+    env = env_cls(**kwargs)
+    if late is not None:
+        env.set_reset_mode(late)
+    return env

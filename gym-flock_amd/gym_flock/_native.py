@@ -126,6 +126,18 @@ COV_MAP_TOO_MANY = 0x2
 COV_MAP_TOO_FEW = 0x4
 COV_MAP_OVERFLOW = 0x8
 
+COV_RESET_SEED = 0x1  # cov_reset_device flags
+COV_RESET_NEW_MAPS = 0x2
+COV_RESET_DONE = 0x4
+COV_RESET_REGION_SHORT = 0x1  # cov_reset_device status bits
+COV_RESET_REGION_SMALL = 0x2
+
+
+class CovResetConfig(ctypes.Structure):
+    _fields_ = [("frac_active", ctypes.c_double), ("nearby", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("seed", ctypes.c_uint64)]
+
+
 COV_ACTIONS_DEVICE = 0x1
 COV_ACTIONS_RESIDENT = 0x2
 COV_ACTIONS_GREEDY = 0x20
@@ -228,6 +240,7 @@ SIGNATURES = {
     "cov_map_lattice": [_P, _P, _P],
     "cov_reset": [_P, _P, _P],
     "cov_reset_seeded": [_P, ctypes.c_uint64, ctypes.c_double, _P, _P],
+    "cov_reset_device": [_P, _P, _P, _P, _P, _P, _P, _P],
     "cov_step": [_P, _P, _I],
     "cov_step_expert": [_P, _I, _P, _P],
     "cov_set_actions": [_P, _P],
@@ -240,6 +253,7 @@ SIGNATURES = {
     "cov_get_robots": [_P, _I, _P, _P],
     "cov_get_visited": [_P, _I, _P],
     "cov_get_n_motion": [_P, _P],
+    "cov_get_n_targets": [_P, _P],
     "cov_sync": [_P],
     "cov_set_streams": [_P, _I],
     "cov_set_tm_plan": [_P, _I, _I],
@@ -1025,6 +1039,38 @@ class CoverageHandle:
                                         ptr(vi) if fetch else None))
         return (st, vi) if fetch else None
 
+    def reset_device(self, mask=None, frac_active=0.5, nearby=0, seed=None, new_maps=False, done=False,
+                     out=None):
+        """reset() of chosen envs on the device (cov_reset_device), each from its own
+        np_random stream where it stands (or RandomState(seed + b) with seed given): mask
+        (B) selects the envs (None: all, or with done=True the envs whose done flag is
+        set); nearby > 0 draws the reference's nearby_starts region of that many nodes
+        (get_n_nearest) around a drawn target; new_maps first draws the selected envs' next
+        maps from their map streams. Every other env is left as it is. Returns (n_reset,
+        start (B,R), visited (B,t_max), region (B,t_max), status (B)); rows of envs that
+        were not selected keep what `out` (the same four arrays) held, or zeros. An env
+        whose region has fewer nodes than robots raises GymFlockError (GF_EINVAL) carrying
+        n_reset and the four arrays; the other selected envs are reset."""
+        if out is None:
+            out = (np.zeros((self.n_envs, self.n_robots), np.int32), np.zeros((self.n_envs, self.t_max), np.uint8),
+                   np.zeros((self.n_envs, self.t_max), np.uint8), np.zeros(self.n_envs, np.int32))
+        st, vi, rg, status = out
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            assert m.shape == (self.n_envs,), m.shape
+        flags = (COV_RESET_SEED if seed is not None else 0) | (COV_RESET_NEW_MAPS if new_maps else 0) | \
+            (COV_RESET_DONE if done else 0)
+        rc = CovResetConfig(float(frac_active), int(nearby), flags, int(seed or 0))
+        n = ctypes.c_int32(0)
+        code = self.lib.cov_reset_device(self.h, ctypes.byref(rc), ptr(m), ptr(st), ptr(vi), ptr(rg), ptr(status),
+                                         ctypes.byref(n))
+        if code:
+            err = GymFlockError(code, self.lib.fe_last_error().decode(errors="replace"))
+            err.n_reset, err.start, err.visited, err.region, err.status = n.value, st, vi, rg, status
+            raise err
+        return n.value, st, vi, rg, status
+
     def step(self, actions=None, resident=False, greedy=False, rng=False):
         """actions (B,R) host ints; or resident=True (the last set/greedy actions); or
         greedy=True: controller(greedy=True)'s actions computed inside the step's launch
@@ -1160,6 +1206,12 @@ class CoverageHandle:
         v = np.empty(self.t_max, np.uint8)
         check(self.lib.cov_get_visited(self.h, int(env), ptr(v)))
         return v
+
+    def n_targets(self):
+        """(B) int32: the targets of each env's current map (cov_get_n_targets)."""
+        n = np.empty(self.n_envs, np.int32)
+        check(self.lib.cov_get_n_targets(self.h, ptr(n)))
+        return n
 
     def n_motion(self):
         n = np.empty(self.n_envs, np.int32)

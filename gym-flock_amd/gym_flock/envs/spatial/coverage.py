@@ -50,8 +50,10 @@ class CoverageEnv(Env):
                  starts=start_regions, unvisiteds=unvisited_regions, init_graph=True,
                  episode_length=EPISODE_LENGTH, res=DELTA, pad_nodes=True, max_nodes=MAX_NODES,
                  nearby_starts=NEARBY_STARTS, horizon=HORIZON, hide_nodes=False,
-                 n_node_feat=N_NODE_FEAT, device=0):
+                 n_node_feat=N_NODE_FEAT, device=0, reset_mode="reference"):
         super(CoverageEnv, self).__init__()
+        self.set_reset_mode(reset_mode)
+        self._defer_region = False  # reset(), device mode: the new graph's region is drawn by the call
         if bool(hide_nodes) != (n_node_feat == N_NODE_FEAT + 1) or n_node_feat not in (N_NODE_FEAT, N_NODE_FEAT + 1):
             raise NotImplementedError("only the reference's shipped configurations are implemented: no hidden "
                                       "nodes with 3 node features, or hide_nodes=True with n_node_feat=4 (ExploreEnv)")
@@ -114,6 +116,15 @@ class CoverageEnv(Env):
         self.np_random, seed = np_random(seed)
         return [seed]
 
+    def set_reset_mode(self, reset_mode):
+        """"reference": reset()'s region, start and unvisited draws run here on
+        self.np_random; "device": in one cov_reset_device call on the same stream, uploaded
+        before the call and read back into the same RandomState after it (the same
+        results). Takes effect at the next reset()."""
+        if reset_mode not in ("reference", "device"):
+            raise ValueError("reset_mode must be \"reference\" or \"device\"")
+        self.reset_mode = reset_mode
+
     def _fixed_node_count(self):
         """Whether every map of this env has the same node count (pad_nodes=False)."""
         return False
@@ -161,7 +172,9 @@ class CoverageEnv(Env):
             self._h.set_targets(self.targets, env=0)
         self._closest = self._greedy_cache = self._motion_cache = None
         self.n_motion_edges = int(self._h.n_motion()[0])
-        if self.nearby_starts:
+        if self._defer_region:
+            self.start_region = None  # set by reset() from cov_reset_device's region
+        elif self.nearby_starts:
             n_nearest = self.get_n_nearest(self.np_random.choice(self.n_targets), self.n_robots * NEARBY_DENSITY)
             region = np.zeros(self.n_targets, bool)
             region[list(n_nearest)] = True
@@ -203,6 +216,8 @@ class CoverageEnv(Env):
         self.episode_reward = 0
         self.step_counter = 0
         self.last_loc = None
+        if self.reset_mode == "device":
+            return self._reset_on_device()
         targets, graph_changed = self._generate_targets()
         if graph_changed:
             self._initialize_graph(targets, on_device=True)
@@ -221,6 +236,30 @@ class CoverageEnv(Env):
         self._h.reset(starts[None], visited)
         self.step_counter = 1
         self._closest = starts.astype(np.int64) + self.n_robots  # robots sit on their start targets
+        self._greedy_cache = None
+        return self._obs()
+
+    def _reset_on_device(self):
+        """reset() with reset_mode="device": the map as in the default mode (its draws come
+        from the global np.random), then the scalar draw, the start region, the starts and
+        the unvisited set in one cov_reset_device call on self.np_random's stream, which
+        the same RandomState object then continues."""
+        self._defer_region = True
+        try:
+            targets, graph_changed = self._generate_targets()
+            if graph_changed:
+                self._initialize_graph(targets, on_device=True)
+        finally:
+            self._defer_region = False
+        self._h.set_rng([self.np_random])
+        nearby = self.n_robots * NEARBY_DENSITY if self.nearby_starts else 0
+        _, start, _, region, _ = self._h.reset_device(None, self.frac_active_targets, nearby)
+        keys, pos = self._h.get_rng()
+        self.np_random.set_state(("MT19937", keys[0], int(pos[0])))
+        self.start_region = region[0, :self.n_targets].astype(bool).tolist()
+        self.unvisited_region = [True] * self.n_targets
+        self.step_counter = 1
+        self._closest = start[0].astype(np.int64) + self.n_robots
         self._greedy_cache = None
         return self._obs()
 

@@ -51,7 +51,7 @@ class CoverageARLEnv(CoverageEnv):
     def __init__(self, n_robots=4, episode_length=50, pad_nodes=True, max_nodes=1000,
                  nearby_starts=True, num_subgraphs=3.0, check_connected=True,
                  downsample_rate=10, perimeter_delta=2.0, horizon=-1, hide_nodes=HIDE_NODES, n_node_feat=3,
-                 occupancy=None, device=0):
+                 occupancy=None, device=0, reset_mode="reference"):
         if occupancy is None:
             occupancy = find_occupancy(downsample_rate)
         if isinstance(occupancy, (str, os.PathLike)):
@@ -72,7 +72,7 @@ class CoverageARLEnv(CoverageEnv):
         super(CoverageARLEnv, self).__init__(n_robots=n_robots, init_graph=False, episode_length=episode_length,
                                              res=MAP_RES * downsample_rate, pad_nodes=pad_nodes, max_nodes=max_nodes,
                                              nearby_starts=nearby_starts, horizon=horizon, hide_nodes=hide_nodes,
-                                             n_node_feat=n_node_feat, device=device)
+                                             n_node_feat=n_node_feat, device=device, reset_mode=reset_mode)
         self.load_graph()
         targets, sampled = self._generate_targets()
         self._initialize_graph(targets, on_device=sampled)

@@ -6,7 +6,9 @@ a robot (not the node a robot stands on: its distance is 0), then masks the node
 of undiscovered nodes, flags discovered nodes next to an undiscovered one in a fourth
 feature, and hides the senders of edges with an undiscovered end (coverage.py:334-346). The
 greedy expert only heads for discovered targets (:819-820). All of it runs on the device
-after the step (cov_set_hidden).
+after the step (cov_set_hidden). The constructor keeps the reference's signature; reset()'s
+draws move to the device with gym_flock.make(..., reset_mode="device") or
+set_reset_mode("device") (CoverageEnv).
 """
 from .coverage_arl import CoverageARLEnv
 

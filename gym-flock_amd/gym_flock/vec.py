@@ -165,8 +165,10 @@ class VecCoverage:
 
     CoverageARL-v0 batches: VecCoverage(B, 4, max_nodes=1000, episode_length=50, res=5.0),
     then load_occupancy(grid); reset(new_maps=True) then samples every env's map from the
-    pool (generate_submaps). The batched reset keeps uniform starts (cov_reset_seeded):
-    the reference's nearby_starts region is drawn by the drop-in CoverageARLEnv only.
+    pool (generate_submaps). reset() draws uniform starts for every env from fresh streams
+    (cov_reset_seeded); reset_envs() resets chosen envs (a mask, an index list, or the envs
+    that are done) from their continued np_random streams on the device, with the
+    reference's nearby_starts region when nearby_starts=True (cov_reset_device).
 
     ExploreEnv batches: the same with hide_nodes=True (and horizon=19). obs(), flat_obs()
     and graphs_tuple() then give the hidden observation (4 node features, hidden senders),
@@ -174,8 +176,10 @@ class VecCoverage:
     """
 
     def __init__(self, n_envs, n_robots, max_nodes=1000, episode_length=75, res=5.5,
-                 frac_active_targets=0.5, device=0, env_offset=0, hide_nodes=False, horizon=10):
+                 frac_active_targets=0.5, device=0, env_offset=0, hide_nodes=False, horizon=10,
+                 nearby_starts=False):
         self.n_envs, self.n_robots = int(n_envs), int(n_robots)
+        self.nearby_starts = bool(nearby_starts)  # reset_envs: nearby = n_robots * NEARBY_DENSITY (5)
         self.frac = frac_active_targets
         self.env_offset = int(env_offset)
         self.hide_nodes = bool(hide_nodes)
@@ -276,6 +280,43 @@ class VecCoverage:
         else:
             self._rngs, self._dev_streams = rngs, False
         return start, visited
+
+    def reset_envs(self, envs=None, new_maps=False, nearby=None, seed=None):
+        """Reset chosen envs on the device and leave every other env as it is, bit for bit
+        (cov_reset_device). envs: None (all), a bool mask (B), a list of env indices, or
+        "done" (the envs whose last step set done). Each selected env continues its own
+        np_random stream (the reference's reset(), coverage.py:398-414), or starts from
+        RandomState(seed + env_offset + b) with seed given; nearby (default: n_robots * 5
+        with nearby_starts=True, else 0) draws the start region of get_n_nearest(choice(T),
+        nearby); new_maps first draws the selected envs' next maps from their map streams.
+        Returns (n_reset, start (B,R), visited (B, max_nodes-R), status (B)); rows of envs
+        that were not reset are zero."""
+        if self._rngs is not None:  # the host holds the streams: back onto the device
+            self.h.set_rng(self._rngs)
+            self._rngs, self._dev_streams = None, True
+        if nearby is None:
+            nearby = self.n_robots * 5 if self.nearby_starts else 0
+        mask, done = None, False
+        if isinstance(envs, str):
+            if envs != "done":
+                raise ValueError("envs: None, a mask, a list of indices or \"done\"")
+            done = True
+        elif envs is not None:
+            e = np.asarray(envs)
+            if e.dtype == bool or e.dtype == np.uint8 and e.shape == (self.n_envs,):
+                mask = e.astype(bool)
+            else:
+                mask = np.zeros(self.n_envs, bool)
+                mask[e.astype(np.int64)] = True
+        sd = None if seed is None else int(seed) + self.env_offset
+        try:
+            n, start, visited, region, status = self.h.reset_device(mask, self.frac, nearby, sd, new_maps, done)
+        finally:
+            if new_maps:  # the selected envs' new sizes
+                self.n_targets[:] = self.h.n_targets()
+        if seed is not None:
+            self._dev_streams = True
+        return n, start, visited, status
 
     def _device_draws(self):
         """Whether the fused greedy step can draw the fallback robots' np_random.choice(4)

@@ -503,6 +503,57 @@ int cov_reset(cov_handle* h, const int32_t* start, const uint8_t* visited);
  * GF_EINVAL where the draws' LDS (2496 + 9 * (max_nodes - R) bytes) exceeds a CU's 160 KB
  * (above 17,927 targets: draw on the host, cov_reset). */
 int cov_reset_seeded(cov_handle* h, uint64_t seed, double frac_active, int32_t* start_out, uint8_t* visited_out);
+
+/* reset() of chosen envs on the device, their np_random streams continued, with the
+ * reference's nearby_starts region (coverage.py:398-414, :596-599, get_n_nearest :655-673). */
+#define COV_RESET_SEED      0x1  /* selected env b starts from RandomState(seed + b); else its stream continues */
+#define COV_RESET_NEW_MAPS  0x2  /* selected envs first draw a new map from their own map streams */
+#define COV_RESET_DONE      0x4  /* env_mask == NULL selects the envs whose done flag is set */
+/* status bits per selected env */
+#define COV_RESET_REGION_SHORT 0x1  /* the region stopped growing below `nearby` nodes (the reference would loop forever) */
+#define COV_RESET_REGION_SMALL 0x2  /* fewer region nodes than robots (numpy raises): env not reset, call fails */
+
+typedef struct {
+  double   frac_active;  /* frac_active_targets, [0,1] */
+  int32_t  nearby;       /* 0: every target may be a start; n > 0: get_n_nearest(choice(T), n) */
+  int32_t  flags;
+  uint64_t seed;         /* COV_RESET_SEED */
+} cov_reset_config;
+
+/* The envs with env_mask[b] != 0 (env_mask NULL: every env, or with COV_RESET_DONE the envs
+ * whose done flag is set) are reset; every other env stays as it is, bit for bit: its
+ * observation (the hidden one included), robots, visited flags, step counter, reward / done,
+ * resident actions, np_random and map streams, map and time matrix. A selected env b draws
+ * from its np_random stream on the device (cov_set_rng / cov_reset_seeded, or seeded here:
+ * COV_RESET_SEED), in the reference's order:
+ *   1. nearby > 0: i = np_random.choice(T), one scalar draw (none when T == 1);
+ *   2. region = {i}; while |region| < nearby: region |= out-neighbours(region) in the motion
+ *      graph, each round from the set as it stood at its start (the set may overshoot
+ *      nearby). A round that adds nothing ends the loop: COV_RESET_REGION_SHORT;
+ *   3. start = members_ascending[permutation(|region|)[:R]]; with nearby == 0 the members are
+ *      all T targets and the draws are cov_reset_seeded's;
+ *   4. unvisited = permutation(T)[:int(T * frac_active)];
+ *   5. cov_reset's pass and observation for the env (discovered := robots on a hidden handle).
+ * COV_RESET_NEW_MAPS: the selected envs first draw their next map from their own map streams,
+ * with cov_generate_submaps' sampler when a pool with num_subgraphs > 1 is loaded, else with
+ * the configuration of the last cov_generate_maps call that drew its cities (GF_ESTATE
+ * without either); only their time matrices and greedy lists become invalid.
+ * Outputs (any may be NULL; rows of unselected envs are left untouched): start_out (B,R),
+ * visited_out and region_out (B, max_nodes - R; region: 1 = a node of the start region),
+ * status_out (B), *n_reset_out the envs reset. An env with fewer region nodes than robots
+ * (COV_RESET_REGION_SMALL) keeps its previous state, though its stream has advanced by the
+ * scalar draw (its start_out row reads -1, its visited_out row 1); the other selected envs
+ * are reset and the call returns GF_EINVAL naming it.
+ * GF_ESTATE: no streams on the device without COV_RESET_SEED; COV_RESET_DONE before any
+ * reset; a first reset that does not take every env. With COV_RESET_DONE and nothing done:
+ * no launch, *n_reset_out = 0, GF_OK. GF_EINVAL before any device work: frac_active outside
+ * [0,1], nearby < 0, unknown flags, seed + n_envs above 2^32, n_robots > 624, or the draws'
+ * LDS (2496 + 9 * (max_nodes - R) + 16 * ceil((max_nodes - R) / 64) bytes) above a CU's
+ * 160 KB (above 17,441 targets). */
+int cov_reset_device(cov_handle* h, const cov_reset_config* rc, const uint8_t* env_mask /* (B) or NULL */,
+                     int32_t* start_out /* (B,R) */, uint8_t* visited_out /* (B,max_nodes-R) */,
+                     uint8_t* region_out /* (B,max_nodes-R) */, int32_t* status_out /* (B) */,
+                     int32_t* n_reset_out);
 /* step(action) (:174-204, :234-364): actions[B][R] in [0,4). */
 int cov_step(cov_handle* h, const int32_t* actions, int flags);
 /* n_steps fused greedy expert steps (COV_ACTIONS_GREEDY | COV_GREEDY_RNG: controller(greedy=
@@ -548,6 +599,7 @@ int cov_get_rewards(cov_handle* h, double* reward, uint8_t* done);   /* (B), (B)
 int cov_get_robots(cov_handle* h, int env, double* xr, int32_t* nodes); /* closest_targets :427 */
 int cov_get_visited(cov_handle* h, int env, uint8_t* visited); /* (max_nodes - R): reset()'s layout */
 int cov_get_n_motion(cov_handle* h, int32_t* n_motion);
+int cov_get_n_targets(cov_handle* h, int32_t* n_targets); /* (B) targets of each env's current map (0: none) */
 /* Launches per cov_step. n = 0 (the default): fused greedy steps (COV_ACTIONS_GREEDY) go
  * out as two half-batch launches on two streams (as fe_set_streams), every other step as
  * one launch, which the device, not the host, bounds (scripts/cov_launch_probe.py); n = 2
