@@ -30,6 +30,12 @@ constexpr int kInlineRimU = 4;      // fused kNN inline rim scan: columns in fli
 constexpr int kStoreTab = 16;      // network rows: float4 table entries per wave (one per nibble)
 constexpr int kNetDeltaBatch = 64;  // delta network store: record words a wave compares at a time
 constexpr size_t kNetDeltaLds = 4 * kNetDeltaBatch * 8;  // their changed bits in LDS, per wave
+// a batch with more dirty groups than this (of 256) takes the row loop instead of the
+// compacted drain (-DGF_NET_COMPACT_MAX for A/B; DESIGN.md §4, "Compacted drain")
+#ifndef GF_NET_COMPACT_MAX
+#define GF_NET_COMPACT_MAX 128
+#endif
+constexpr int kNetCompactMax = GF_NET_COMPACT_MAX;
 constexpr int kStepInlineRim = 2;  // fused kNN: unranked rows a wave ranks itself (more: rim kernel)
 constexpr int kStepExactKnnMax = 128;  // fused kNN: envs up to this size are ranked exactly in
                                        // the step (KX: one tile in LDS, no rim kernel)

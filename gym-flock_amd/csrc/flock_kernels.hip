@@ -702,8 +702,12 @@ __device__ __forceinline__ void store_network_rows(const StepArgs& a, const uint
 // time: whole rows per batch while a row has at most that many words, 64-word chunks of
 // one row beyond. Lane l holds word l of a batch; the batches' recorded words are loaded
 // two ahead (the first two before the degrees are summed), so their round trip is off the
-// store loop. The batch's changed bits (recorded ^ new) go to the wave's own LDS words,
-// from which every lane takes those of its float4's group.
+// store loop. From its word's changed bits (recorded ^ new) every lane derives the flags of
+// the word's four 64-byte groups; the batch's dirty groups are then listed in the wave's
+// own LDS words and drained four lanes to a group (the compacted drain, below). A forced
+// launch, a batch that is mostly dirty and the 16- and 128-byte builds keep the row loop:
+// the changed bits go to those LDS words, from which every lane takes those of its
+// float4's group.
 struct NetDelta {
   int r0, nr;        // the wave's rows of the block
   int cpr, rpb, nb;  // 64-word chunks per row, rows per batch (cpr == 1), batches
@@ -768,41 +772,109 @@ __device__ __forceinline__ void store_network_rows_delta(const StepArgs& a, cons
   const unsigned* adj32 = reinterpret_cast<const unsigned*>(adj);
   const unsigned* fl32 = reinterpret_cast<const unsigned*>(dfl);
   const int o0 = (lane & 7) << 2;  // this lane's float4: its nibble of a 32-bit word
+  // set bits take the row's value, clear ones +0.0f
+  auto row_f4 = [](unsigned nib, unsigned ivb) {
+    f4v v;
+    v.x = __uint_as_float(ivb & (0u - (nib & 1u)));
+    v.y = __uint_as_float(ivb & (0u - ((nib >> 1) & 1u)));
+    v.z = __uint_as_float(ivb & (0u - ((nib >> 2) & 1u)));
+    v.w = __uint_as_float(ivb & (0u - ((nib >> 3) & 1u)));
+    return v;
+  };
+  // Compacted drain (64-byte groups, net_delta.h): unless the launch is forced or most of
+  // the batch is dirty, the batch's dirty groups are listed in the wave's LDS words, one
+  // byte each, and stored four lanes to a group: ceil(D / 16) wave stores for D dirty
+  // groups instead of one per 1 KiB of every row.
+  constexpr bool kCompact = kNetGroupBytes == 64;
+  const unsigned rdiv = net_compact_rdiv(Wn);
+  const int lrow = static_cast<int>((static_cast<unsigned>(lane) * rdiv) >> 16);  // batch row of this lane's word
+  unsigned char* ent = reinterpret_cast<unsigned char*>(dfl);
+  const unsigned* invb = reinterpret_cast<const unsigned*>(inv);
+  const int sl = lane >> 2, f4i = lane & 3;  // the drain: entry 16 it + sl, float4 f4i of its group
   for (int b = 0; b < d.nb; ++b) {
     const uint64_t old = d.o0;
     d.o0 = d.o1;
     d.o1 = net_delta_load(a, d, Wn, grow0, b + 2, lane);
     const NetDeltaBatch t = net_delta_batch(d, Wn, b);
+    uint64_t nw = 0, x = 0;
     if (lane < t.cnt) {
-      const uint64_t nw = adj[(size_t)d.r0 * Wn + t.wf + lane];
-      const uint64_t x = force ? ~0ull : (old ^ nw);
-      dfl[lane] = x;
+      nw = adj[(size_t)d.r0 * Wn + t.wf + lane];
+      x = force ? ~0ull : (old ^ nw);
       if (x) a.net_bits[gr0 * (size_t)Wn + t.wf + lane] = nw;
     }
-    // the wave's LDS operations run in order: the words above precede the reads below,
-    // which precede the next batch's words (the fences keep the compiler to that order)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const int nqc = min(nq - (t.cw0 << 4), kNetDeltaBatch * 16);  // float4s of a row in this batch
-    for (int rr = 0; rr < t.nrb; ++rr) {
-      const int m = t.m0 + rr, r = d.r0 + m;
-      const bool vc = (vmask >> m) & 1ull;
-      const unsigned ivb = __float_as_uint(inv[r]);
-      f4v* r4 = reinterpret_cast<f4v*>(a.network + (grow0 + r) * (size_t)N) + (t.cw0 << 4);
-      const unsigned* nrow = adj32 + ((size_t)r * Wn + t.cw0) * 2;
-      const unsigned* frow = fl32 + (d.cpr == 1 ? rr * Wn * 2 : 0);
-      for (int q = lane; q < nqc; q += 64) {
-        const unsigned nw32 = nrow[q >> 3];
-        if (net_group_dirty<kNetGroupBytes>(net_delta_bits(frow[q >> 3], nw32, vc), o0)) {
-          // set bits take the row's value, clear ones +0.0f
-          const unsigned nib = nw32 >> o0;
-          f4v v;
-          v.x = __uint_as_float(ivb & (0u - (nib & 1u)));
-          v.y = __uint_as_float(ivb & (0u - ((nib >> 1) & 1u)));
-          v.z = __uint_as_float(ivb & (0u - ((nib >> 2) & 1u)));
-          v.w = __uint_as_float(ivb & (0u - ((nib >> 3) & 1u)));
-          r4[q] = v;
+    // the batch's dirty groups: lane l's word has quarter k dirty = bit l of qm[k]
+    [[maybe_unused]] unsigned flags = 0;
+    [[maybe_unused]] uint64_t qm[4] = {0, 0, 0, 0};
+    int D = 0;
+    bool dense = true;
+    if constexpr (kCompact) {
+      if (!force) {
+        flags = net_word_flags(x, nw, (vmask >> ((t.m0 + lrow) & 63)) & 1ull);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          qm[k] = __ballot((flags >> k) & 1u);
+          D += __popcll(qm[k]);
         }
+        dense = D > kNetCompactMax;
+      }
+    }
+    if (dense) {
+      if (lane < t.cnt) dfl[lane] = x;
+      // the wave's LDS operations run in order: the words above precede the reads below,
+      // which precede the next batch's words (the fences keep the compiler to that order)
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      const int nqc = min(nq - (t.cw0 << 4), kNetDeltaBatch * 16);  // float4s of a row in this batch
+      for (int rr = 0; rr < t.nrb; ++rr) {
+        const int m = t.m0 + rr, r = d.r0 + m;
+        const bool vc = (vmask >> m) & 1ull;
+        const unsigned ivb = __float_as_uint(inv[r]);
+        f4v* r4 = reinterpret_cast<f4v*>(a.network + (grow0 + r) * (size_t)N) + (t.cw0 << 4);
+        const unsigned* nrow = adj32 + ((size_t)r * Wn + t.cw0) * 2;
+        const unsigned* frow = fl32 + (d.cpr == 1 ? rr * Wn * 2 : 0);
+        for (int q = lane; q < nqc; q += 64) {
+          const unsigned nw32 = nrow[q >> 3];
+          if (net_group_dirty<kNetGroupBytes>(net_delta_bits(frow[q >> 3], nw32, vc), o0))
+            r4[q] = row_f4(nw32 >> o0, ivb);
+        }
+      }
+    } else if (D > 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if ((flags >> k) & 1u) ent[net_compact_slot(qm, k, lane)] = static_cast<unsigned char>(net_compact_entry(lane, k));
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      // entry e = (word << 2) | quarter is also the index of the group's 16 new bits among
+      // the batch's adjacency words. The reads run ahead of the stores: an entry two
+      // iterations ahead, its group's bits and its row's value one iteration ahead.
+      const unsigned short* a16 = reinterpret_cast<const unsigned short*>(adj + (size_t)d.r0 * Wn + t.wf);
+      const unsigned* ivr = invb + d.r0 + t.m0;
+      f4v* n4 = reinterpret_cast<f4v*>(a.network + (gr0 + t.m0) * (size_t)N);
+      const int nit = (D + 15) >> 4;
+      auto entry = [&](int it) {  // 0 past the list's end (its float4 is not stored)
+        const int i = (it << 4) + sl;
+        const unsigned e = ent[i & (kNetCompactSlots - 1)];
+        return i < D ? e : 0u;
+      };
+      auto group = [&](unsigned e, unsigned& ab, unsigned& iv, NetCompactDst& to) {
+        to = net_compact_dst(e, f4i, Wn, rdiv, t.cw0, nq);
+        ab = a16[e];
+        iv = ivr[to.row];
+      };
+      unsigned ab0, iv0, e1;
+      NetCompactDst t0;
+      group(entry(0), ab0, iv0, t0);
+      e1 = entry(1);
+      for (int it = 0; it < nit; ++it) {
+        const unsigned e2 = entry(it + 2);
+        unsigned ab1, iv1;
+        NetCompactDst t1;
+        group(e1, ab1, iv1, t1);
+        if ((it << 4) + sl < D && t0.ok) n4[t0.row * nq + t0.q] = row_f4(ab0 >> (f4i << 2), iv0);
+        ab0 = ab1;
+        iv0 = iv1;
+        t0 = t1;
+        e1 = e2;
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -973,7 +1045,8 @@ __device__ unsigned long long gf_stamp_buf[8192 * 16];
 // epilogue every row is ranked exactly against the whole env, staged in LDS as the tile
 // (below): no keys in the feature pass, no unranked rows, no rim kernel.
 // DN (the plain step only: no CTRL, VAR, KN, UIN, KX): the network rows go out in their
-// delta form (store_network_rows_delta), against the record in StepArgs.net_bits / net_val.
+// delta form (store_network_rows_delta), against the record in StepArgs.net_bits / net_val,
+// and pass 1 leaves the float32 superset of the adjacency for the feature pass to decide.
 template <bool DYN, bool UF64, bool CTRL, bool VAR, int PF = 0, int KN = 0, bool UIN = false, int KX = 0,
           bool DN = false>
 __global__ __launch_bounds__(kThreads, VAR ? 1
@@ -1015,7 +1088,11 @@ void flock_step_kernel(typename std::conditional<UIN, StepArgsU, StepArgs>::type
   // every such pair's float64 r2 to rank it, decides the adjacency exactly and writes the
   // exact words back, so every tile's feature pass runs before the network stores
   constexpr bool kSupK = KN > 0 && !CTRL;
-  constexpr bool kSup = kOuter || kSupK;
+  // the delta instantiation of the plain step (kSupD) takes the same path: its feature pass
+  // computes every set pair's float64 r2 as well (the expression the band sweep used), so
+  // pass 1 needs one compare per pair instead of two and no band sweep
+  constexpr bool kSupD = DN;
+  constexpr bool kSup = kOuter || kSupK || kSupD;
   uint64_t* nearb = adj + (size_t)R * Wn;                      // R x Wt controller bits (KN && CTRL)
   uint64_t* candb = nearb + ((CTRL && !kOuter) ? (size_t)R * Wt : 0);  // (predicted rows) x Wt kNN candidates
   double* red = reinterpret_cast<double*>(candb + (KN ? (size_t)R * Wt : 0));
@@ -1120,7 +1197,10 @@ void flock_step_kernel(typename std::conditional<UIN, StepArgsU, StepArgs>::type
       isnear = r2 <= a.cr;
       if (!isadj && !isnear) return isadj;
     }
-    if constexpr (kSupK) isadj = r2 < a.cr2;  // a superset or candidate bit: decided here (:117)
+    if constexpr (kSupK || kSupD) isadj = r2 < a.cr2;  // a superset or candidate bit: decided here (:117)
+    if constexpr (kSupD) {
+      if (!isadj) return isadj;  // a float32 superset pair past comm_radius: no features
+    }
     if constexpr (KN > 0) {
       if (!GF_ABLATE(a, 0x200000)) {  // diag 0x200000: no insertion (timing only)
         // q = min(ceil(r2 * ksc), qmax): qmax - (qmax - r2 * ksc truncated; negative or
@@ -1189,7 +1269,7 @@ void flock_step_kernel(typename std::conditional<UIN, StepArgsU, StepArgs>::type
         continue;
       }
       const uint64_t cm = (KN && crow) ? crow[w] : 0ull;
-      if constexpr (kSupK) {  // superset and candidates in, the exact adjacency word out
+      if constexpr (kSupK || kSupD) {  // superset and candidates in, the exact adjacency word out
         // am covers the adjacency, so clearing the bit of every pair found not adjacent
         // (the rare float32 superset pairs past comm_radius, and a predicted row's
         // candidates, whose bits may not be set) leaves the exact word; an LDS atomic
@@ -1311,7 +1391,7 @@ void flock_step_kernel(typename std::conditional<UIN, StepArgsU, StepArgs>::type
           if (lane < nrows) ptc[lane] = tcr_l;  // read back by this wave only (in-order LDS)
         }
       }
-      if constexpr (kSupK) {
+      if constexpr (kSupK || kSupD) {
         // one compare per column: the float32 superset of the adjacency (the feature pass
         // decides it exactly), plus the predicted rows' candidates when most rows are
         // predicted. Rows in pairs; the rows past nrows sit far away in rxy (columns past
@@ -1510,7 +1590,7 @@ void flock_step_kernel(typename std::conditional<UIN, StepArgsU, StepArgs>::type
     if (ti < 2) GF_STAMP(3 + 3 * ti);
 
     // pass 2 (features) of every tile but the last runs here; the last tile's runs
-    // after the network stores are issued, so the stores drain under it (kOuter: the
+    // after the network stores are issued, so the stores drain under it (kSup: the
     // stores need the exact adjacency this pass writes, so every tile's runs here)
     if (kSup || j0 + T < N) {
       feature_pass(j0, nch);

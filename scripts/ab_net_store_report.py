@@ -39,6 +39,7 @@ def main():
                 gain, stat["parent"][0] / stat["delta"][0], spread))
             print("  every delta run below every parent run: %s" % (stat["delta"][2] < stat["parent"][1]))
             print("  median difference >= 2 x largest spread: %s" % (gain >= 2 * spread))
+            print("  median difference / largest spread: %.1f" % (gain / spread if spread > 0 else float("inf")))
             if "full" in stat:
                 print("  full overlaps parent: %s" % (stat["full"][1] <= stat["parent"][2]
                                                         and stat["parent"][1] <= stat["full"][2]))

@@ -5,7 +5,10 @@
 # handle's first launch is the forced full store that fills the record).
 # LIBS="name=path ...": libraries to run beside this tree's (parent: GYMFLOCK_NET_STORE
 # unset; any other name: with =delta, e.g. another -DGF_NET_GROUP_BYTES).
-# usage: [N=1024 B=256] [STEPS=6] [OUT=out] [LIBS=...] scripts/pmc_net_store.sh
+# COUNTERS="A B ...": the counters (default FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU; any other,
+# such as SQ_INSTS_VMEM_WR, is reported beside them). MODES="full delta": which store modes
+# of this tree's library to run.
+# usage: [N=1024 B=256] [STEPS=6] [OUT=out] [LIBS=...] [COUNTERS=...] [MODES=...] scripts/pmc_net_store.sh
 set -o pipefail
 cd "$(dirname "$0")/.." || exit 1
 OUT=${OUT:-out}
@@ -18,10 +21,11 @@ pass() {  # name counter env...
   env "$@" timeout -k 10 180 rocprofv3 --pmc "$ctr" --output-format csv -d "$D/${name}_$ctr" -o pmc -- \
     python scripts/pmc_step.py >"$D/${name}_$ctr.log" 2>&1
 }
-NAMES="full delta"
-for ctr in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU; do
-  pass full "$ctr" GYMFLOCK_NET_STORE=full || exit 1
-  pass delta "$ctr" GYMFLOCK_NET_STORE=delta || exit 1
+export COUNTERS=${COUNTERS:-FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU}
+MODES=${MODES-full delta}
+NAMES="$MODES"
+for ctr in $COUNTERS; do
+  for m in $MODES; do pass "$m" "$ctr" "GYMFLOCK_NET_STORE=$m" || exit 1; done
   for kv in $LIBS; do
     name=${kv%%=*}
     if [ "$name" = parent ]; then pass "$name" "$ctr" "GYMFLOCK_LIB=${kv#*=}" || exit 1

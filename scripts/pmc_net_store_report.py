@@ -3,7 +3,8 @@
 JSON: for every variant the launches' FETCH_SIZE / WRITE_SIZE (KiB), SQ_INSTS_VALU and
 the HBM bytes (2 * FETCH_SIZE + WRITE_SIZE) * 1024 (gfx950: FETCH_SIZE reports half the
 bytes of a wide read, MI355X_MICROARCH.md, HBM), the first launch (a delta handle's forced
-full store) apart from the mean of the others.
+full store) apart from the mean of the others. COUNTERS in the environment (as
+pmc_net_store.sh exports it) names the counters that were collected.
 
 usage: pmc_net_store_report.py DIR VARIANT..."""
 import csv
@@ -29,12 +30,12 @@ def main():
     out = {}
     for n in names:
         e = {}
-        for ctr in ("FETCH_SIZE", "WRITE_SIZE", "SQ_INSTS_VALU"):
+        for ctr in os.environ.get("COUNTERS", "FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU").split():
             rows = launches(d, n, ctr)
             vals = [v for _, _, v in rows]
             e["kernel"] = rows[-1][1]
             e[ctr] = {"first_launch": vals[0], "later_mean": sum(vals[1:]) / len(vals[1:]), "later": vals[1:]}
-        for k in ("first_launch", "later_mean"):
+        for k in ("first_launch", "later_mean") if "FETCH_SIZE" in e and "WRITE_SIZE" in e else ():
             e["hbm_bytes_" + k] = (2 * e["FETCH_SIZE"][k] + e["WRITE_SIZE"][k]) * 1024
         out[n] = e
     print(json.dumps(out, indent=1))
