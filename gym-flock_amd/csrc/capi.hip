@@ -146,6 +146,7 @@ void release(fe_handle* h) {
                   h->adj_bits[0], h->adj_bits[1], h->pdeg[0], h->pdeg[1], h->net_bits, h->net_val};
   for (void* p : bufs)
     if (p) hipFree(p);
+  if (h->roll_stage) hipFree(h->roll_stage);
   if (h->fin_cnt) hipFree(h->fin_cnt);
   if (h->fin_host) hipHostFree(h->fin_host);
   for (void* p : {(void*)h->rng_key, (void*)h->rng_pos, (void*)h->reset_tries, (void*)h->reset_status,
@@ -327,6 +328,7 @@ int net_store_mode(fe_handle* h, gf::StepArgs& a, bool ctrl) {
   a.net_val = nullptr;
   a.net_force = 0;
   if (!a.network || a.network != h->net) return GF_OK;
+  h->net_stale = false;  // the launch writes the handle's buffer (fe_step_expert left it behind)
   const bool eligible = h->net_store == FE_NET_DELTA && !ctrl && !a.variant && !a.knn_idx && !a.u_inline &&
                         (a.N & 3) == 0 && !a.diag;
   if (!eligible) {
@@ -967,6 +969,100 @@ int fe_step(fe_handle* h, const void* u, int flags) {
   return GF_OK;
 }
 
+int fe_step_expert(fe_handle* h, int n_steps, const fe_rollout* rec) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  const int N = h->cfg.n_agents, B = h->cfg.n_envs;
+  if (n_steps < 1) return fail(GF_EINVAL, "fe_step_expert: n_steps must be >= 1");
+  if (N > gf::kRolloutMaxN)
+    return fail(GF_EINVAL, "fe_step_expert: a rollout keeps an env's state in LDS, n_agents <= 256; beyond, loop over "
+                           "fe_step(FE_U_EXPERT | FE_WITH_CONTROLLER)");
+  const int every = rec ? rec->record_every : 1;
+  if (rec) {
+    if (rec->flags & ~FE_ROLLOUT_DEVICE) return fail(GF_EINVAL, "fe_step_expert: unknown flag");
+    if (every < 1 || n_steps % every != 0) return fail(GF_EINVAL, "fe_step_expert: record_every must be >= 1 and divide n_steps");
+  }
+  if (!h->has_state) return fail(GF_ESTATE, "state not set (call fe_set_state first)");
+  if (!h->has_ctrl) return fail(GF_ESTATE, "FE_U_EXPERT needs a previous controller output");
+  if (h->met.comm)
+    return fail(GF_ESTATE, "fe_step_expert: the handle has a communicator (its metrics ring holds 64 steps); step it with fe_step");
+  if (int rc = use_dev(h)) return rc;  // after both halves of the latest split step
+  if (int rc = next_reward_slot(h)) return rc;
+
+  gf::RolloutArgs a{};
+  a.s = base_args(h);
+  a.s.x_in = h->x[h->cur];
+  a.s.x_out = h->x[h->cur ^ 1];
+  a.s.u = h->ctrl[h->ccur];
+  a.s.ctrl_out = h->ctrl[h->ccur ^ 1];
+  a.s.state_values = h->sv;
+  a.s.reward = cur_reward(h);
+  int bw = -1;
+  if (int rc = packed_outputs(h, true, a.s, &bw)) return rc;
+  a.n_steps = n_steps;
+  a.record_every = every;
+
+  // records: the caller's device memory, or the staging buffer for host destinations
+  const size_t K = (size_t)(n_steps / every), KBN = K * h->BN, Wn = ((size_t)N + 63) / 64;
+  const bool to_host = rec && !(rec->flags & FE_ROLLOUT_DEVICE);
+  struct Part {
+    void* dst;
+    size_t bytes, off;
+  } parts[6] = {};
+  if (rec) {
+    parts[0] = {rec->x, KBN * 4 * sizeof(double), 0};
+    parts[1] = {rec->state_values, KBN * 6 * sizeof(float), 0};
+    parts[2] = {rec->adj_bits, KBN * Wn * sizeof(uint64_t), 0};
+    parts[3] = {rec->degree, KBN * sizeof(int32_t), 0};
+    parts[4] = {rec->controls, KBN * 2 * sizeof(double), 0};
+    parts[5] = {rec->rewards, (size_t)n_steps * B * sizeof(double), 0};
+  }
+  void* dev[6] = {};
+  if (to_host) {
+    size_t total = 0;
+    for (Part& q : parts)
+      if (q.dst) {
+        q.off = total;
+        total += (q.bytes + 255) & ~(size_t)255;
+      }
+    if (total > h->roll_stage_bytes) {
+      // whatever read the old buffer was waited for by the call that issued it
+      if (h->roll_stage) GF_HIP(hipFree(h->roll_stage));
+      h->roll_stage = nullptr;
+      h->roll_stage_bytes = 0;
+      if (int rc = dalloc(&h->roll_stage, total)) return rc;
+      h->roll_stage_bytes = total;
+    }
+    for (int k = 0; k < 6; ++k)
+      if (parts[k].dst) dev[k] = h->roll_stage + parts[k].off;
+  } else {
+    for (int k = 0; k < 6; ++k) dev[k] = parts[k].dst;
+  }
+  a.rec_x = static_cast<double*>(dev[0]);
+  a.rec_sv = static_cast<float*>(dev[1]);
+  a.rec_bits = static_cast<uint64_t*>(dev[2]);
+  a.rec_deg = static_cast<int32_t*>(dev[3]);
+  a.rec_ctrl = static_cast<double*>(dev[4]);
+  a.rec_rewards = static_cast<double*>(dev[5]);
+
+  if (hipError_t e = gf::launch_rollout(a, h->stream); e != hipSuccess) return fail_hip("flock_rollout_kernel launch", e);
+  GF_HIP(clear_knn_history(h));
+  h->cur ^= 1;
+  h->ccur ^= 1;
+  h->bits_cur = bw;
+  h->has_ctrl = h->has_obs = h->has_packed = true;
+  h->obs_on_host = false;
+  h->has_knn = false;
+  h->net_stale = true;           // the dense network still describes the state before the rollout
+  h->net_record_valid = false;   // and the next plain step stores it in full
+  if (to_host) {
+    for (int k = 0; k < 6; ++k)
+      if (parts[k].dst)
+        GF_HIP(hipMemcpyAsync(parts[k].dst, dev[k], parts[k].bytes, hipMemcpyDeviceToHost, h->stream));
+    GF_HIP(hipStreamSynchronize(h->stream));
+  }
+  return GF_OK;
+}
+
 // fe_step_host and fe_step_host_knn: knn_idx / knn_obs (either non-NULL) also rank the new
 // state's k nearest (the fused selection, or the kNN kernel) and bring them back.
 static int step_host_impl(fe_handle* h, const void* u, float* state_values, float* network, double* rewards,
@@ -1263,6 +1359,7 @@ int fe_get_network(fe_handle* h, int env, float* dst) {
   if (int rc = check_env(h, env)) return rc;
   if (!h->has_obs) return fail(GF_ESTATE, "no observation computed yet");
   if (h->obs_on_host) return fail(GF_ESTATE, "the last step wrote its observations to host arrays (fe_step_host)");
+  if (h->net_stale) return fail(GF_ESTATE, "the dense network was not written by fe_step_expert (fe_compute_helpers first)");
   if (int rc = use_dev(h)) return rc;
   const size_t n = (size_t)h->cfg.n_agents * h->cfg.n_agents;
   return env < 0 ? d2h(h, dst, h->net, h->BN * h->cfg.n_agents * 4) : d2h(h, dst, h->net + env * n, n * 4);
@@ -1273,6 +1370,7 @@ int fe_get_network_rows(fe_handle* h, int env, int row0, int nrows, float* dst) 
     return fail(GF_EINVAL, "bad argument");
   if (int rc = check_env(h, env)) return rc;
   if (!h->has_obs || h->obs_on_host) return fail(GF_ESTATE, "no device observation (none yet, or fe_step_host wrote it to host arrays)");
+  if (h->net_stale) return fail(GF_ESTATE, "the dense network was not written by fe_step_expert (fe_compute_helpers first)");
   if (int rc = use_dev(h)) return rc;
   const size_t N = h->cfg.n_agents;
   return d2h(h, dst, h->net + (env * N + row0) * N, (size_t)nrows * N * 4);
@@ -1313,6 +1411,7 @@ int fe_get_outputs(fe_handle* h, int env, float* state_values, float* network, d
   if (!h->has_obs) return fail(GF_ESTATE, "no observation computed yet");
   if (h->obs_on_host && (state_values || network))
     return fail(GF_ESTATE, "the last step wrote its observations to host arrays (fe_step_host)");
+  if (h->net_stale && network) return fail(GF_ESTATE, "the dense network was not written by fe_step_expert (fe_compute_helpers first)");
   if (int rc = use_dev(h)) return rc;
   const size_t N = h->cfg.n_agents;
   const size_t nsv = env < 0 ? h->BN * 6 : N * 6, nnet = env < 0 ? h->BN * N : N * N;

@@ -159,6 +159,12 @@ struct fe_handle {
   int32_t* pdeg[2] = {nullptr, nullptr};       // (B,N)
   int bits_cur = 0;                     // buffer of the latest bits / degrees
   bool has_packed = false;
+  // fe_step_expert: the rollout leaves the dense network buffer as it was (its getters
+  // return GF_ESTATE until a launch writes it again), and records for host destinations
+  // go through a device staging buffer (grow-only)
+  bool net_stale = false;
+  unsigned char* roll_stage = nullptr;
+  size_t roll_stage_bytes = 0;
   // Flocking-v0 pipelining: the kNN of step t runs on kstream, after both halves of
   // step t and beside step t+1. A step that writes the state buffer x[i] (or a bits
   // buffer) an unfinished kNN reads waits for that kNN's event first; every other API

@@ -178,6 +178,29 @@ struct ResetArgs {
 size_t reset_lds_bytes(int N, bool reject);
 hipError_t launch_reset(const ResetArgs& a, hipStream_t s);
 
+// The closed-loop expert rollout (flock_rollout.hip): n_steps of u = controller();
+// step(u) in one launch, one workgroup (of up to 1024 threads) per env that keeps the env's
+// state in LDS.
+constexpr int kRolloutMaxN = 256;  // every size at which the reference's reset() accepts a draw
+struct RolloutArgs {
+  // The constants, variant switches and per-env dt of a step (base_args), and the handle's
+  // buffers: x_in / u (float64) the state and its controller output before the first step;
+  // x_out, ctrl_out, state_values, adj_bits, degree_out and reward are written by the last
+  // step (any may be nullptr).
+  StepArgs s;
+  int n_steps;
+  int record_every;       // >= 1: record step t when (t + 1) % record_every == 0
+  // records (K = n_steps / record_every), each (K,B,N,.) or nullptr
+  double* rec_x;          // (K,B,N,4)
+  float* rec_sv;          // (K,B,N,6)
+  uint64_t* rec_bits;     // (K,B,N,Wn)
+  int32_t* rec_deg;       // (K,B,N)
+  double* rec_ctrl;       // (K,B,N,2)
+  double* rec_rewards;    // (n_steps,B): every step's
+};
+int rollout_chunk_bits(int N);  // columns per pass-2 thread: 16, 32, 64 for N <= 64, 128, 256
+hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s);
+
 // Launch-geometry helpers shared by host and tests.
 int step_rows_per_block(int N);
 int step_tile(int N);

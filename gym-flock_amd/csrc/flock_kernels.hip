@@ -19,6 +19,7 @@
 // Numerics: the pair path is float64 with -ffp-contract=off so every r2 is the
 // reference's bit pattern (dx*dx + dy*dy, two roundings then a sum); adjacency is
 // therefore bit-exact, and features differ from NumPy only by summation order.
+#include "flock_dynamics.h"
 #include "flock_internal.h"
 #include "net_delta.h"
 
@@ -38,10 +39,6 @@ namespace {
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f2v __attribute__((ext_vector_type(2)));
-
-struct __attribute__((aligned(16))) St {
-  double px, py, vx, vy;
-};
 
 // Workgroup -> (env, row block) with all row blocks of an env on one XCD
 // (blocks b and b+8 share an XCD under round-robin dispatch; speed only).
@@ -86,61 +83,14 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 // (redf), and in slot 6 an int flag: some agent of the env has a NaN coordinate.
 constexpr int kNanFlagSlot = 6;
 
-// State of agent `g` (flat index b*N + j) after the double-integrator update of
-// flocking_relative.py:96-105, in the reference's operation order. With a float32 u
-// the action terms are float32 arithmetic (NumPy keeps u*10.0, *dt, *0.5 in float32)
-// and are widened when added to the float64 state.
-template <class V>
-__device__ __forceinline__ V clip_sym(V v, V c) {  // np.clip(v, -c, c); NaN stays NaN
-  return v < -c ? -c : (v > c ? c : v);
-}
-
-// The variants' update (oracle/flocking_variants.integrate): optional clip, the
-// step's own action scale, per-env dt, the frozen agents' float64 mask applied after
-// the action arithmetic, and the stochastic env's state scaling around the update.
+// State of agent `g` (flat index b*N + j) after the variants' update
+// (flock_dynamics.h: integrate_variant) with the env's own dt.
 template <bool UF64>
 __device__ St load_state_variant(const StepArgs& a, size_t g, double2 p, double2 v) {
   const int b = static_cast<int>(g / static_cast<size_t>(a.N));
   const int j = static_cast<int>(g - static_cast<size_t>(b) * a.N);
   const double dt = a.dt_env ? a.dt_env[b] : a.dt;
-  const double m = j < a.n_frozen ? 0.0 : 1.0;
-  const double S = a.x_scale;
-  const double px = p.x * S, py = p.y * S, vx = v.x * S, vy = v.y * S;
-  double apx, apy, avx, avy;
-  if constexpr (UF64) {
-    const double2 u = reinterpret_cast<const double2*>(a.u)[g];
-    double ux = u.x, uy = u.y;
-    if (a.u_clip > 0) {
-      ux = clip_sym(ux, a.u_clip);
-      uy = clip_sym(uy, a.u_clip);
-    }
-    ux *= a.u_scale;
-    uy *= a.u_scale;
-    apx = (((ux * dt) * dt) * 0.5) * m;
-    apy = (((uy * dt) * dt) * 0.5) * m;
-    avx = (ux * dt) * m;
-    avy = (uy * dt) * m;
-  } else {
-    const float2 u = reinterpret_cast<const float2*>(a.u)[g];
-    const float dtf = static_cast<float>(dt);
-    float ux = u.x, uy = u.y;
-    if (a.u_clip > 0) {
-      ux = clip_sym(ux, a.uc_f);
-      uy = clip_sym(uy, a.uc_f);
-    }
-    ux *= a.us_f;
-    uy *= a.us_f;
-    apx = static_cast<double>(((ux * dtf) * dtf) * 0.5f) * m;
-    apy = static_cast<double>(((uy * dtf) * dtf) * 0.5f) * m;
-    avx = static_cast<double>(ux * dtf) * m;
-    avy = static_cast<double>(uy * dtf) * m;
-  }
-  St s;
-  s.px = ((px + vx * dt) + apx) / S;
-  s.py = ((py + vy * dt) + apy) / S;
-  s.vx = (vx + avx) / S;
-  s.vy = (vy + avy) / S;
-  return s;
+  return integrate_variant<UF64>(a, dt, j, p, v, reinterpret_cast<const ActionT<UF64>*>(a.u)[g]);
 }
 
 // The global loads behind one agent's post-update state, and the update itself: split
@@ -165,26 +115,8 @@ __device__ __forceinline__ RawState<UF64> load_raw(const StepArgs& a, size_t g) 
 
 template <bool DYN, bool UF64>
 __device__ __forceinline__ St state_from_raw(const StepArgs& a, const RawState<UF64>& r) {
-  const double2 p = r.p, v = r.v;
-  St s{p.x, p.y, v.x, v.y};
-  if constexpr (DYN) {
-    if constexpr (UF64) {
-      const double ux = r.u.x * a.action_scalar, uy = r.u.y * a.action_scalar;
-      s.px = (p.x + v.x * a.dt) + ((ux * a.dt) * a.dt) * 0.5;
-      s.py = (p.y + v.y * a.dt) + ((uy * a.dt) * a.dt) * 0.5;
-      s.vx = v.x + ux * a.dt;
-      s.vy = v.y + uy * a.dt;
-    } else {
-      const float ux = r.u.x * a.as_f, uy = r.u.y * a.as_f;
-      const float apx = ((ux * a.dt_f) * a.dt_f) * 0.5f;
-      const float apy = ((uy * a.dt_f) * a.dt_f) * 0.5f;
-      s.px = (p.x + v.x * a.dt) + static_cast<double>(apx);
-      s.py = (p.y + v.y * a.dt) + static_cast<double>(apy);
-      s.vx = v.x + static_cast<double>(ux * a.dt_f);
-      s.vy = v.y + static_cast<double>(uy * a.dt_f);
-    }
-  }
-  return s;
+  if constexpr (DYN) return integrate_plain<UF64>(a, r.p, r.v, r.u);
+  else return St{r.p.x, r.p.y, r.v.x, r.v.y};
 }
 
 template <bool DYN, bool UF64, bool VAR = false>
@@ -426,10 +358,6 @@ __device__ __forceinline__ void step_inline_rim(const StepArgs& a, size_t env0, 
       reinterpret_cast<float4*>(a.knn_obs)[g * KN + lane] = ob;
     }
   }
-}
-
-__device__ __forceinline__ double clip10(double v) {  // np.clip(v, -10, 10); NaN stays NaN
-  return v < -10.0 ? -10.0 : (v > 10.0 ? 10.0 : v);
 }
 
 // float32 prefilter band for one threshold: a pair whose float32 r2 (from float32-

@@ -33,6 +33,8 @@ FE_OUT_MAPPED = 0x1  # fe_get_outputs flag
 FE_RESET_SEED = 0x1  # fe_reset_device flags
 FE_RESET_NO_REJECT = 0x2
 FE_RESET_EXHAUSTED = 0x1  # fe_reset_device status bit
+FE_ROLLOUT_DEVICE = 0x1  # fe_rollout flag: the record pointers are device memory
+FE_ROLLOUT_MAX_AGENTS = 256
 
 
 class FeConfig(ctypes.Structure):
@@ -55,6 +57,12 @@ class FeVariant(ctypes.Structure):
     _fields_ = [("n_frozen", ctypes.c_int32), ("n_vel_zero", ctypes.c_int32),
                 ("u_scale", ctypes.c_double), ("u_clip", ctypes.c_double),
                 ("x_scale", ctypes.c_double), ("ctrl_clip", ctypes.c_double)]
+
+
+class FeRollout(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("state_values", ctypes.c_void_p), ("adj_bits", ctypes.c_void_p),
+                ("degree", ctypes.c_void_p), ("controls", ctypes.c_void_p), ("rewards", ctypes.c_void_p),
+                ("record_every", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
 class FeResetConfig(ctypes.Structure):
@@ -184,6 +192,7 @@ SIGNATURES = {
     "fe_set_actions": [_P, _P, _I],
     "fe_compute_helpers": [_P, _I],
     "fe_step": [_P, _P, _I],
+    "fe_step_expert": [_P, _I, ctypes.POINTER(FeRollout)],
     "fe_step_host": [_P, _P, _P, _P, _P, _P, _I],
     "fe_step_host_knn": [_P, _P, _P, _P, _P, _P, _P, _I],
     "fe_step_host_knn_ctrl": [_P, _P, _P, _P, _P, _P, _P, _P, _I],
@@ -677,6 +686,43 @@ class FlockHandle:
             u = np.ascontiguousarray(u)
             assert u.shape == (self.n_envs, self.n_agents, 2), u.shape
             check(self.lib.fe_step(self.h, ptr(u), int(flags)))
+
+    def rollout_shapes(self, n_steps, every=1):
+        """name -> (shape, dtype) of fe_step_expert's records (fe_rollout)."""
+        k, b, n = n_steps // every, self.n_envs, self.n_agents
+        return {"x": ((k, b, n, 4), np.float64), "state_values": ((k, b, n, 6), np.float32),
+                "adj_bits": ((k, b, n, (n + 63) // 64), np.uint64), "degree": ((k, b, n), np.int32),
+                "controls": ((k, b, n, 2), np.float64), "rewards": ((n_steps, b), np.float64)}
+
+    def step_expert(self, n_steps, record=(), every=1, fetch=True, device_ptrs=None):
+        """n_steps of u = controller(); step(u) in one launch (fe_step_expert), from a state
+        that has a controller output. record: names among x, state_values, adj_bits, degree,
+        controls (after every `every`-th step; `every` divides n_steps) and rewards (every
+        step's); shapes in rollout_shapes(). Returns a dict of host arrays and waits for
+        them. device_ptrs: {name: device address} of caller-owned buffers of those shapes,
+        written in stream order instead (only enqueues, returns None; `record` is ignored).
+        fetch=False (and no device_ptrs): nothing is recorded, only enqueues, returns
+        None; the getters then give the last step's outputs."""
+        n_steps, every = int(n_steps), int(every)
+        shapes = self.rollout_shapes(max(n_steps, 0), max(every, 1))
+        rec = FeRollout()
+        rec.record_every = every
+        out = None
+        if device_ptrs is not None:
+            for name, addr in device_ptrs.items():
+                if name not in shapes:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+                setattr(rec, name, ctypes.c_void_p(int(addr)))
+            rec.flags = FE_ROLLOUT_DEVICE
+        elif fetch:
+            out = {}
+            for name in record:
+                if name not in shapes:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+                out[name] = np.empty(*shapes[name])
+                setattr(rec, name, out[name].ctypes.data_as(ctypes.c_void_p))
+        check(self.lib.fe_step_expert(self.h, n_steps, ctypes.byref(rec)))
+        return out
 
     def step_host(self, u_addr, f64, sv, net, rew, ctrl):
         """fe_step_host: one launch and one wait. u_addr: address of (B,N,2) host actions

@@ -116,6 +116,28 @@ class VecFlockingRelative:
         else:
             self.h.step(u, flags)
 
+    def expert_steps(self, n_steps, record=("rewards",), every=1, fetch=True, device_ptrs=None):
+        """n_steps of the expert loop u = controller(); step(u) for every env in ONE launch
+        (fe_step_expert, n_agents <= 256), for demonstrations: the same states, adjacency
+        and degrees as n_steps calls of step(expert=True, controller=True,
+        network="packed"), bit for bit. Needs a controller output of the current state
+        (controller(), or a step with controller=True).
+        record: what to keep of every `every`-th step (`every` divides n_steps), among
+        "x" (K,B,N,4), "state_values" (K,B,N,6), "adj_bits" (K,B,N,ceil(N/64)) uint64,
+        "degree" (K,B,N), "controls" (K,B,N,2) (the controller of the recorded state) with
+        K = n_steps // every, and "rewards" (n_steps,B), always every step's. Returns a
+        dict of arrays. device_ptrs={name: device address}: those records are written to
+        the caller's device buffers in stream order instead (e.g. tensor.data_ptr());
+        nothing waits and None is returned, as with fetch=False (nothing recorded).
+        Afterwards get_state(), controls(), rewards(), state_values() and network_packed()
+        are the last step's; network() raises until compute_helpers() or a step that
+        writes the dense network."""
+        return self.h.step_expert(n_steps, record, every, fetch, device_ptrs)
+
+    def compute_helpers(self):
+        """compute_helpers() on the current state: every observation buffer anew."""
+        self.h.compute_helpers()
+
     def set_actions(self, u):
         self.h.set_actions(u)
 

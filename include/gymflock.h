@@ -184,6 +184,47 @@ int fe_compute_helpers(fe_handle* h, int flags);
  * optionally fused controller() (:194-226) and Flocking-v0 kNN (flocking.py:20-25).
  * u: (B,N,2) float32 or float64 (FE_U_F64), host or device (FE_U_DEVICE). Async. */
 int fe_step(fe_handle* h, const void* u, int flags);
+/* The expert loop `u = env.controller(); env.step(u)` for n_steps steps in ONE launch, with
+ * optional recording (expert demonstrations: the reference README's imitation learning).
+ * The same as n_steps calls of fe_step(h, NULL, FE_U_EXPERT | FE_WITH_CONTROLLER |
+ * FE_PACKED_NETWORK | FE_NO_NETWORK): states, adjacency bits and degrees bit for bit,
+ * state_values, controls and rewards up to summation order (every sum runs in a fixed tree:
+ * two runs give the same bits, whatever n_steps and record_every are). One workgroup keeps
+ * an env's state in LDS across all steps, so n_agents <= 256 (every size at which the
+ * reference's reset() ever accepts a draw); GF_EINVAL above: loop over
+ * fe_step(FE_U_EXPERT) there. Variants (fe_set_variant) and a per-env dt (fe_set_dt, the
+ * same dt for all n_steps) apply as in fe_step.
+ * rec (or NULL: nothing recorded): where to put step t's record for every t with
+ * (t + 1) % record_every == 0, K = n_steps / record_every of them, and every step's reward.
+ * Every pointer may be NULL (not recorded). */
+typedef struct fe_rollout {
+  double*   x;            /* (K,B,N,4)  state after the step                       */
+  float*    state_values; /* (K,B,N,6)                                             */
+  uint64_t* adj_bits;     /* (K,B,N,ceil(N/64)) layout of fe_get_network_packed    */
+  int32_t*  degree;       /* (K,B,N)                                               */
+  double*   controls;     /* (K,B,N,2)  controller() of the state after the step   */
+  double*   rewards;      /* (n_steps,B) every step's, whatever record_every is    */
+  int32_t   record_every; /* >= 1 and divides n_steps                              */
+  int32_t   flags;        /* FE_ROLLOUT_DEVICE: the pointers are caller-owned device memory */
+} fe_rollout;
+#define FE_ROLLOUT_DEVICE 0x1
+/* Runs on the handle's stream after both halves of the latest split step. With rec NULL or
+ * FE_ROLLOUT_DEVICE the call only enqueues (device destinations are written by the kernel
+ * itself, in stream order); with host destinations the records go through a device staging
+ * buffer kept on the handle and the call returns when they are in place.
+ * GF_ESTATE without a controller output of the current state (fe_controller, or a step
+ * with FE_WITH_CONTROLLER), and on a handle with a communicator (the metrics ring holds 64
+ * steps). GF_EINVAL for n_steps < 1, record_every < 1 or not dividing n_steps, unknown
+ * flags, n_agents > 256.
+ * Afterwards the handle is as after fe_set_state with a controller output: the final state
+ * and its controls are the handle's, fe_get_rewards returns the last step's rewards,
+ * fe_get_state_values and fe_get_network_packed the last step's. The dense network was not
+ * written: fe_get_network, fe_get_network_rows and fe_get_outputs (network) return
+ * GF_ESTATE until a launch writes it (fe_compute_helpers, a step without FE_NO_NETWORK),
+ * and the next plain step stores it in full (as after fe_network_touched). fe_get_knn
+ * ranks the final state anew. Closed-loop stepping, or another rollout, goes on without a
+ * new fe_controller. */
+int fe_step_expert(fe_handle* h, int n_steps, const fe_rollout* rec /* or NULL */);
 /* The drop-in env's step(u) (:91-109) as one launch and one wait, for small batches
  * where latency, not bandwidth, counts (FlockingRelativeEnv.step, N ~ 100-1000, B = 1).
  * u: (B,N,2) host actions, float32 or float64 (FE_U_F64). One env of at most one tile
