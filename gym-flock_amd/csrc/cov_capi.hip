@@ -1898,6 +1898,93 @@ int cov_get_hidden_obs(cov_handle* h, int env, float* nodes4, int32_t* senders, 
   return check_err(h);
 }
 
+int64_t cov_explore_lds_bytes(int n_robots, int max_nodes) {
+  if (n_robots < 1 || max_nodes < n_robots) return -1;
+  return (int64_t)gf::cov_explore_lds_layout(n_robots, max_nodes, nullptr, nullptr);
+}
+
+// n_steps expert steps of a handle that hides nodes in one launch (cov_explore_multi_kernel);
+// equal to n_steps times cov_controller_greedy, the host's fallback draws, cov_set_actions and
+// the resident cov_step with its hidden pass.
+int cov_explore_expert(cov_handle* h, int n_steps, const cov_rollout* rec) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->hidden) return fail(GF_ESTATE, "cov_explore_expert: the handle does not hide nodes (cov_set_hidden); cov_step_expert is its form");
+  if (!h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
+  if (!h->mt_key) return fail(GF_ESTATE, "set the envs' np_random streams first (cov_set_rng or cov_reset_seeded)");
+  if (n_steps < 1) return fail(GF_EINVAL, "n_steps must be at least 1");
+  const int every = rec ? rec->record_every : 1;
+  if (every < 1 || n_steps % every != 0) return fail(GF_EINVAL, "record_every must be at least 1 and divide n_steps");
+  if (rec && (rec->flags & ~COV_ROLLOUT_DEVICE)) return fail(GF_EINVAL, "unknown cov_rollout flags");
+  const int R = h->cfg.n_robots, M = h->cfg.max_nodes;
+  if (R > gf::kMtN) return fail(GF_EINVAL, "n_robots <= 624 (one key regeneration per step)");
+  const size_t lds = gf::cov_explore_lds_layout(R, M, nullptr, nullptr);
+  if (lds > gf::kCovExploreLdsMax)
+    return fail(GF_EINVAL, "cov_explore_expert: " + std::to_string(lds) + " bytes of LDS per workgroup exceed 64 KB (cov_explore_lds_bytes)");
+  if (M - R > gf::kGreedyListMaxT)
+    return fail(GF_EINVAL, "the fused expert needs max_nodes - n_robots <= 1024 (the greedy lists)");
+  if (int rc = use(h)) return rc;
+  if (!h->tm_ready || !h->tm_glist)
+    if (int rc = ensure_time_matrix(h)) return rc;
+  if (!h->tm_glist) return fail(GF_EINVAL, "the fused expert needs max_nodes - n_robots <= 1024 (the greedy lists)");
+  if (int rc = join_s2(h)) return rc;
+  gf::CovArgsX x{};
+  x.a = h->a;
+  x.a.actions = nullptr;
+  x.a.glist = h->tm_glist;
+  x.a.glen = h->tm_glen;
+  x.a.gstride = h->gstride;
+  x.a.gcost = h->tm_cost;
+  x.a.gprev = h->tm_prevT;
+  x.a.gactions = h->actions;
+  x.a.needs_random = h->needs_random;
+  x.a.mt_key = h->mt_key;
+  x.a.mt_pos = h->mt_pos;
+  x.h = hidden_args(h);
+  x.n_steps = n_steps;
+  x.record_every = every;
+  const size_t B = h->cfg.n_envs, n = (size_t)n_steps * B, K = (size_t)(n_steps / every);
+  const size_t L = (size_t)16 * M + 1;
+  const bool dev = rec && (rec->flags & COV_ROLLOUT_DEVICE);
+  // host destinations: one scratch block, each record 16-byte aligned
+  size_t off[5] = {0, 0, 0, 0, 0}, bytes[5] = {0, 0, 0, 0, 0};
+  unsigned char* buf = nullptr;
+  if (rec && dev) {
+    x.reward_k = rec->rewards;
+    x.done_k = rec->done;
+    x.act_k = rec->actions;
+    x.nrand_k = rec->needs_random;
+    x.flat_k = rec->flat_obs;
+  } else if (rec) {
+    const void* dst[5] = {rec->rewards, rec->done, rec->actions, rec->needs_random, rec->flat_obs};
+    const size_t want[5] = {n * 8, n, n * R * 4, n * R, K * B * L * 4};
+    size_t total = 0;
+    for (int k = 0; k < 5; ++k) {
+      off[k] = total;
+      bytes[k] = dst[k] ? want[k] : 0;
+      total += (bytes[k] + 15) & ~(size_t)15;
+    }
+    if (total) {
+      if (int rc = scratch(h, total, &buf)) return rc;
+      if (bytes[0]) x.reward_k = reinterpret_cast<double*>(buf + off[0]);
+      if (bytes[1]) x.done_k = buf + off[1];
+      if (bytes[2]) x.act_k = reinterpret_cast<int32_t*>(buf + off[2]);
+      if (bytes[3]) x.nrand_k = buf + off[3];
+      if (bytes[4]) x.flat_k = reinterpret_cast<float*>(buf + off[4]);
+    }
+  }
+  hipError_t e = gf::launch_cov_explore_multi(x, h->stream);
+  if (e != hipSuccess) return fail(GF_EHIP, std::string("cov_explore_multi_kernel: ") + hipGetErrorString(e));
+  h->main_dirty = true;
+  h->other_work = true;
+  if (!buf) return GF_OK;
+  void* dst[5] = {rec->rewards, rec->done, rec->actions, rec->needs_random, rec->flat_obs};
+  for (int k = 0; k < 5; ++k)
+    if (bytes[k])
+      if (int rc = copy_out(h, dst[k], buf + off[k], bytes[k])) return rc;
+  GF_HIP(hipStreamSynchronize(h->stream));
+  return check_err(h);
+}
+
 int cov_sync(cov_handle* h) {
   if (!h) return fail(GF_EINVAL, "null handle");
   if (int rc = use(h)) return rc;

@@ -525,6 +525,31 @@ hipError_t launch_cov_hidden_graphs(const CovHiddenArgs& a, const float* edges_i
                                     float* edges, int32_t* snd, int32_t* rcv, hipStream_t s);
 
 size_t cov_step_lds_bytes(int R, int M);
+
+// cov_explore_expert: n_steps greedy expert steps of envs that hide nodes in one launch
+// (cov_explore_multi_kernel, coverage_kernels.hip), each env's workgroup stepping its env
+// n_steps times with the discovered set kept as bits in LDS. a: the step's arguments with the
+// greedy lists and the streams set; h: the hidden pass's. Records (any may be nullptr):
+// every step's reward, done flag, actions and needs-random flags, and after every
+// record_every-th step the env's hidden flat row (cov_flat_obs_kernel's, nf = 4, float32).
+struct CovArgsX {
+  CovArgs a;
+  CovHiddenArgs h;
+  int n_steps, record_every;
+  int hid_off, tg_off;    // cov_explore_lds_layout's byte offsets into the dynamic LDS
+  double* reward_k;       // (n_steps,B)
+  uint8_t* done_k;        // (n_steps,B)
+  int32_t* act_k;         // (n_steps,B,R)
+  uint8_t* nrand_k;       // (n_steps,B,R)
+  float* flat_k;          // (n_steps / record_every,B,16M+1)
+};
+// The kernel's dynamic LDS: the step's region (cov_step_lds_bytes), then from *hid_off the
+// hidden pass's (cov_hidden_lds_bytes: robot positions, discovered and frontier bits) with
+// four counters, then from *tg_off the env's target positions, which the discovery reads
+// every step. Returns the total; the host's guard and the launcher both take it from here.
+size_t cov_explore_lds_layout(int R, int M, int* hid_off, int* tg_off);
+constexpr size_t kCovExploreLdsMax = 64 * 1024;
+hipError_t launch_cov_explore_multi(const CovArgsX& x, hipStream_t s);
 // cov_seed_reset_kernel's LDS: the stream's key, the permutation, its draws and the flags
 size_t cov_seed_reset_lds_bytes(int Tmax);
 // Observation wire formats: the flat FlattenDictWrapper rows (B, (12 + nf) M + 1), nf

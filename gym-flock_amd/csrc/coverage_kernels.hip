@@ -15,6 +15,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "coverage_hidden.h"
 #include "coverage_internal.h"
 
 namespace gf {
@@ -287,9 +288,17 @@ __device__ __forceinline__ int action_node(const int32_t* nbr, const int32_t* cn
 // One step of env b (a.env0 + blockIdx.x in the kernels below, an entry of a device list in
 // cov_step_list_kernel): MULTI also records the step's
 // reward and done flag at [it][b] of reward_k / done_k.
-template <int NT, bool MULTI>
+// HID (cov_explore_multi_kernel, a greedy step of an env that hides nodes): the expert masks
+// the targets that are visited OR undiscovered (controller :817-821; dbits: the env's
+// discovered set as node bits in LDS), and their count, summed into *nm_s (zero on entry)
+// by the waves that build the mask, stands where the visited count decides how the expert
+// picks; a robot that moves also leaves its new position in xr_lds[i].
+template <int NT, bool MULTI, bool HID = false>
 __device__ __forceinline__ void cov_step_body(const CovArgs& a, const int b, [[maybe_unused]] int it,
-                                              [[maybe_unused]] double* reward_k, [[maybe_unused]] uint8_t* done_k) {
+                                              [[maybe_unused]] double* reward_k, [[maybe_unused]] uint8_t* done_k,
+                                              [[maybe_unused]] const uint32_t* dbits = nullptr,
+                                              [[maybe_unused]] int* nm_s = nullptr,
+                                              [[maybe_unused]] double2* xr_lds = nullptr) {
   constexpr int RPT = kCovThreads / NT;  // robots per thread when R <= kCovThreads
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int R = a.R, M = a.M, Tm = a.Tmax, E = 4 * M;
@@ -394,18 +403,29 @@ __device__ __forceinline__ void cov_step_body(const CovArgs& a, const int b, [[m
   const bool dirty = a.dirty[b] != 0;
   const int nv0 = a.nvisited[b], sc0 = a.step_counter[b];
   const bool full = dirty || !has_act;  // recompute every robot's action edges
-  const bool any_vis = nv0 > 0;
+  bool any_vis = nv0 > 0;
+  int nmask = nv0;  // the targets the expert masks
   if (greedy || a.next_greedy) {
     // the env's visited flags as bits, before this step marks any (ballots, no atomics),
     // read after the robots' loads are in flight
     const int lane = tid & 63, wv = tid >> 6;
+    [[maybe_unused]] int nm_w = 0;
     for (int t0 = wv * 64; t0 < Tm; t0 += NT) {
       const int t = t0 + lane;
-      const uint64_t m = __ballot(t < T && vis[t]);
+      uint64_t m;
+      if constexpr (HID) {
+        m = __ballot(t < T && (vis[t] || !hid_bit(dbits, R + t)));
+        nm_w += __popcll(m);
+      } else {
+        m = __ballot(t < T && vis[t]);
+      }
       if (lane == 0) {
         gvis[t0 >> 5] = static_cast<uint32_t>(m);
         gvis[(t0 >> 5) + 1] = static_cast<uint32_t>(m >> 32);
       }
+    }
+    if constexpr (HID) {
+      if (lane == 0 && nm_w) atomicAdd(nm_s, nm_w);
     }
     if (rng_pre) {  // the prefetched key into its LDS words (read by the draws below)
       uint32_t* kb = reinterpret_cast<uint32_t*>(ulist + kGreedyDirectMax + 1);
@@ -414,9 +434,13 @@ __device__ __forceinline__ void cov_step_body(const CovArgs& a, const int b, [[m
         if (tid + j * NT < kMtN) kb[tid + j * NT] = kpre[j];
     }
     __syncthreads();
+    if constexpr (HID) {  // the reference's column-0 quirk follows the joined mask
+      nmask = *nm_s;
+      any_vis = nmask > 0;
+    }
   }
   // few targets left unvisited: the greedy actions from the short candidate list
-  const bool gdirect = greedy && T - nv0 <= kGreedyDirectMax;
+  const bool gdirect = greedy && T - nmask <= kGreedyDirectMax;
   if (gdirect) {
     greedy_direct_list(gvis, T, any_vis, ulist, ucount);
     __syncthreads();
@@ -459,7 +483,7 @@ __device__ __forceinline__ void cov_step_body(const CovArgs& a, const int b, [[m
       const size_t row = (size_t)b * Tm + (c - R);
       const int g = gdirect ? greedy_direct(a.gcost + row * Tm, a.gprev + row * Tm, nbr + 4 * (c - R), cnt[c - R],
                                             ulist, *ucount)
-                            : greedy_from_list(a.glist + row * a.gstride, a.glen + row, gvis, any_vis, nv0 >= T);
+                            : greedy_from_list(a.glist + row * a.gstride, a.glen + row, gvis, any_vis, nmask >= T);
       const uint32_t flag = static_cast<uint32_t>(g) >> 2;
       if (flag & kGreedyErr) atomicOr(a.err, 8);
       const bool rnd = flag & kGreedyRnd;
@@ -687,6 +711,7 @@ __device__ __forceinline__ void cov_step_body(const CovArgs& a, const int b, [[m
       q = make_int4(__float_as_int(r0.x), __float_as_int(r0.y), __float_as_int(r0.z), __float_as_int(r0.w));
       d = r1;
       *reinterpret_cast<float4*>(xr + 2 * i) = r2;
+      if constexpr (HID) *reinterpret_cast<float4*>(xr_lds + i) = r2;
     } else {  // a robot that does not move keeps its position (:198)
       int4 q4;
       int nc;
@@ -839,6 +864,85 @@ __global__ __launch_bounds__(NT) void cov_step_multi_kernel(CovArgsM p) {
   }
 }
 
+// Element k of an env's FlattenDictWrapper row (cov_flat_obs_kernel below has the layout)
+template <class V>
+__device__ __forceinline__ V cov_flat_value(size_t k, size_t M, size_t N, const float* nodes, const float* edges,
+                                            const int32_t* snd, const int32_t* rcv, const int64_t* step) {
+  if (k < N) return static_cast<V>(nodes[k]);
+  if (k < N + 4 * M) return static_cast<V>(edges[k - N]);
+  if (k < N + 8 * M) return static_cast<V>(snd[k - N - 4 * M]);
+  if (k < N + 12 * M) return static_cast<V>(rcv[k - N - 8 * M]);
+  return static_cast<V>(*step);
+}
+
+// cov_explore_expert: the expert rollout of envs that hide nodes (ExploreEnv), n_steps
+// iterations per workgroup as in cov_step_multi_kernel. The env's discovered set lives as
+// bits in LDS for the whole launch (loaded once from the persistent bytes), with the robots'
+// and the targets' positions beside it. An iteration is
+//   - the greedy step with the expert's mask visited | undiscovered (cov_step_body<HID>: the
+//     mask is built from the visited flags, loaded with the robots' loads, and the LDS bits);
+//   - this step's actions and needs-random flags into the records;
+//   - the hidden pass's own code (cov_hidden_body<KEPT>): discovery from the robots' new
+//     positions, which the movers left in LDS (LDS only, but for the byte of each newly
+//     discovered target), and, on a recorded iteration and on the last one only, the rest of
+//     the pass (the 4M-slot sweep, the node rows, the expert's mask bytes and the counts);
+//   - on a recorded iteration the env's flat row from what the workgroup has just written.
+// So an iteration that is not recorded has the step's two dependent global round trips and
+// no more. What an iteration reads of earlier global writes was written by this workgroup,
+// ordered by the barriers (as in cov_step_multi_kernel).
+template <int NT>
+__global__ __launch_bounds__(NT) void cov_explore_multi_kernel(CovArgsX p) {
+  static_assert(NT == kHidThreads, "the hidden pass's loops stride by its own workgroup size");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const CovArgs& a = p.a;
+  const CovHiddenArgs& h = p.h;
+  const int b = a.env0 + blockIdx.x;
+  const int R = a.R, M = a.M, Tm = a.Tmax, W = (M + 31) >> 5;
+  const int T = min(a.ntg[b], Tm);
+  const int tid = threadIdx.x;
+  double2* xr_s = reinterpret_cast<double2*>(smem + p.hid_off);  // (R) robot positions
+  uint32_t* dbits = reinterpret_cast<uint32_t*>(xr_s + R);        // (W) discovered
+  uint32_t* fbits = dbits + W;                                    // (W) frontier
+  int* nm_s = reinterpret_cast<int*>(fbits + W) + 2;              // after the pass's two counters: the expert's count
+  double2* tg_s = reinterpret_cast<double2*>(smem + p.tg_off);    // (T) target positions
+  const double2* xr = reinterpret_cast<const double2*>(a.xr) + (size_t)b * R;
+  const double2* tg = reinterpret_cast<const double2*>(a.tgt) + (size_t)b * Tm;
+  uint8_t* disc = h.discovered + (size_t)b * M;
+  for (int i = tid; i < R; i += NT) xr_s[i] = xr[i];
+  for (int t = tid; t < T; t += NT) tg_s[t] = tg[t];
+  for (int w = tid; w < W; w += NT) dbits[w] = hid_robot_word(w, R);
+  if (tid == 0) *nm_s = 0;
+  __syncthreads();
+  for (int t = tid; t < T; t += NT)
+    if (disc[R + t]) atomicOr(&dbits[(R + t) >> 5], 1u << ((R + t) & 31));
+  __syncthreads();
+  const int n = p.n_steps > 1 ? p.n_steps : 1;
+  const size_t L = (size_t)16 * M + 1;
+  for (int it = 0; it < n; ++it) {
+    cov_step_body<NT, true, true>(a, b, it, p.reward_k, p.done_k, dbits, nm_s, xr_s);
+    const bool rec = p.flat_k && (it + 1) % p.record_every == 0;
+    const size_t row = ((size_t)it * a.B + b) * R;
+    if (p.act_k)
+      for (int i = tid; i < R; i += NT) p.act_k[row + i] = a.gactions[(size_t)b * R + i];
+    if (p.nrand_k)
+      for (int i = tid; i < R; i += NT) p.nrand_k[row + i] = a.needs_random[(size_t)b * R + i];
+    if (tid == 0) *nm_s = 0;
+    // the body's barrier after the moves orders the new positions and its reads of dbits
+    cov_hidden_body<true>(h, b, smem + p.hid_off, tg_s, rec || it == n - 1);
+    if (rec) {
+      __syncthreads();  // the node rows and the hidden senders, written by other waves
+      float* out = p.flat_k + ((size_t)((it + 1) / p.record_every - 1) * a.B + b) * L;
+      const float* hn = h.hnodes + (size_t)b * M * 4;
+      const float* edges = a.edges + (size_t)b * 4 * M;
+      const int32_t* hs = h.hsenders + (size_t)b * 4 * M;
+      const int32_t* rcv = a.receivers + (size_t)b * 4 * M;
+      for (size_t k = tid; k < L; k += NT)
+        out[k] = cov_flat_value<float>(k, (size_t)M, (size_t)4 * M, hn, edges, hs, rcv, a.obs_step + b);
+    }
+    __syncthreads();
+  }
+}
+
 // cov_reset_device: the observation pass (a.actions == nullptr) of the envs of a device list,
 // entries < 0 skipped. A kernel of its own: the step's arguments and code stay as they are.
 template <int NT>
@@ -942,18 +1046,7 @@ __global__ __launch_bounds__(kCovThreads) void cov_flat_obs_kernel(CovArgs a, in
   const int32_t* snd = a.senders + (size_t)b * E;
   const int32_t* rcv = a.receivers + (size_t)b * E;
   for (size_t k = (size_t)blockIdx.x * kCovThreads + threadIdx.x; k < L; k += (size_t)gridDim.x * kCovThreads) {
-    V v;
-    if (k < N)
-      v = static_cast<V>(nodes[k]);
-    else if (k < N + 4 * M)
-      v = static_cast<V>(edges[k - N]);
-    else if (k < N + 8 * M)
-      v = static_cast<V>(snd[k - N - 4 * M]);
-    else if (k < N + 12 * M)
-      v = static_cast<V>(rcv[k - N - 8 * M]);
-    else
-      v = static_cast<V>(a.obs_step[b]);
-    out[k] = v;
+    out[k] = cov_flat_value<V>(k, M, N, nodes, edges, snd, rcv, a.obs_step + b);
   }
 }
 
@@ -1071,6 +1164,23 @@ hipError_t launch_cov_step_multi(const CovArgsM& m, hipStream_t s) {
   void* args[] = {const_cast<CovArgsM*>(&m)};
   return hipLaunchKernel(reinterpret_cast<const void*>(&cov_step_multi_kernel<kCovThreads>), dim3(m.a.B),
                          dim3(kCovThreads), args, cov_step_lds_bytes(m.a.R, m.a.M), s);
+}
+
+size_t cov_explore_lds_layout(int R, int M, int* hid_off, int* tg_off) {
+  const size_t hid = (cov_step_lds_bytes(R, M) + 15) & ~(size_t)15;
+  const size_t tg = (hid + cov_hidden_lds_bytes(R, M) + 16 + 15) & ~(size_t)15;
+  if (hid_off) *hid_off = (int)hid;
+  if (tg_off) *tg_off = (int)tg;
+  return tg + (size_t)(M - R) * 16;
+}
+
+hipError_t launch_cov_explore_multi(const CovArgsX& x, hipStream_t s) {
+  CovArgsX p = x;
+  const size_t lds = cov_explore_lds_layout(p.a.R, p.a.M, &p.hid_off, &p.tg_off);
+  if (lds > kCovExploreLdsMax) return hipErrorInvalidValue;
+  void* args[] = {&p};
+  return hipLaunchKernel(reinterpret_cast<const void*>(&cov_explore_multi_kernel<kCovThreads>), dim3(p.a.B),
+                         dim3(kCovThreads), args, lds, s);
 }
 
 hipError_t launch_cov_step(const CovArgs& a, hipStream_t s) {

@@ -65,6 +65,25 @@ class FeRollout(ctypes.Structure):
                 ("record_every", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
+class CovRollout(ctypes.Structure):
+    _fields_ = [("rewards", ctypes.c_void_p), ("done", ctypes.c_void_p), ("actions", ctypes.c_void_p),
+                ("needs_random", ctypes.c_void_p), ("flat_obs", ctypes.c_void_p),
+                ("record_every", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+COV_ROLLOUT_DEVICE = 0x1  # cov_rollout flag: the record pointers are device memory
+
+
+def cov_rollout_shapes(n_steps, n_envs, n_robots, max_nodes, every=1):
+    """name -> (shape, dtype) of cov_explore_expert's records (cov_rollout): every step's
+    rewards, done, actions and needs_random, and the hidden flat rows (16 * max_nodes + 1
+    wide, float32) after every `every`-th step."""
+    k, b, r = n_steps // every, n_envs, n_robots
+    return {"rewards": ((n_steps, b), np.float64), "done": ((n_steps, b), np.uint8),
+            "actions": ((n_steps, b, r), np.int32), "needs_random": ((n_steps, b, r), np.uint8),
+            "flat_obs": ((k, b, 16 * max_nodes + 1), np.float32)}
+
+
 class FeResetConfig(ctypes.Structure):
     _fields_ = [("r_max", ctypes.c_double), ("v_max", ctypes.c_double), ("v_bias", ctypes.c_double),
                 ("min_dist", ctypes.c_double), ("min_degree", ctypes.c_int32),
@@ -274,6 +293,8 @@ SIGNATURES = {
     "cov_get_graphs_tuple": [_P, _P, _P, _P, _P, _P, _P, _P, _I],
     "cov_set_hidden": [_P, _I],
     "cov_get_hidden_obs": [_P, _I, _P, _P, _P],
+    "cov_explore_expert": [_P, _I, ctypes.POINTER(CovRollout)],
+    "cov_explore_lds_bytes": [_I, _I],
     "gu_create": [_I, ctypes.POINTER(_P)],
     "gu_destroy": [_P],
     "gu_radius_edges": [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_double, _I,
@@ -302,7 +323,7 @@ SIGNATURES = {
     "fe_kernel_timing": [_P, _I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)],
     "cov_kernel_timing": [_P, _I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)],
 }
-_RESTYPE = {"fe_last_error": ctypes.c_char_p}
+_RESTYPE = {"fe_last_error": ctypes.c_char_p, "cov_explore_lds_bytes": ctypes.c_int64}
 
 _lib = None
 
@@ -1139,6 +1160,43 @@ class CoverageHandle:
         d = np.empty((int(n_steps), self.n_envs), np.uint8) if fetch else None
         check(self.lib.cov_step_expert(self.h, int(n_steps), ptr(r) if fetch else None, ptr(d) if fetch else None))
         return (r, d.astype(bool)) if fetch else None
+
+    def rollout_shapes(self, n_steps, every=1):
+        """name -> (shape, dtype) of cov_explore_expert's records (cov_rollout)."""
+        return cov_rollout_shapes(n_steps, self.n_envs, self.n_robots, self.max_nodes, every)
+
+    def explore_expert(self, n_steps, record=(), every=1, fetch=True, device_ptrs=None):
+        """n_steps of the hidden-node expert (controller(greedy=True) with hide_nodes and its
+        fallback draws, then step and the discovery) in one launch (cov_explore_expert), on a
+        handle with set_hidden. record: names among rewards, done, actions, needs_random
+        (every step's) and flat_obs (the hidden flat row after every `every`-th step; `every`
+        divides n_steps); shapes in rollout_shapes(). Returns a dict of host arrays and
+        waits for them. device_ptrs: {name: device address} of caller-owned buffers of those
+        shapes, written in stream order instead (only enqueues, returns None; `record` is
+        ignored). fetch=False (and no device_ptrs): nothing is recorded, only enqueues,
+        returns None; the getters then give the last step's outputs. flat_obs[k] is what the
+        expert saw when it chose actions[(k + 1) * every]; flat_obs(f32=True) before the call
+        is what it saw for actions[0]."""
+        n_steps, every = int(n_steps), int(every)
+        shapes = self.rollout_shapes(max(n_steps, 0), max(every, 1))
+        rec = CovRollout()
+        rec.record_every = every
+        out = None
+        if device_ptrs is not None:
+            for name, addr in device_ptrs.items():
+                if name not in shapes:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+                setattr(rec, name, ctypes.c_void_p(int(addr)))
+            rec.flags = COV_ROLLOUT_DEVICE
+        elif fetch:
+            out = {}
+            for name in record:
+                if name not in shapes:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+                out[name] = np.empty(*shapes[name])
+                setattr(rec, name, out[name].ctypes.data_as(ctypes.c_void_p))
+        check(self.lib.cov_explore_expert(self.h, n_steps, ctypes.byref(rec)))
+        return out
 
     def set_actions(self, actions):
         a = np.ascontiguousarray(np.asarray(actions).reshape(self.n_envs, self.n_robots), dtype=np.int32)

@@ -347,6 +347,13 @@ class VecCoverage:
         <= 1024). Never with hidden nodes: the fused step does not know the discovered set."""
         return not self.hide_nodes and self._dev_streams and self._rngs is None and self.n_robots <= 624 and self.h.t_max <= 1024
 
+    def _explore_fused(self):
+        """Whether a greedy step of a hidden batch can run as one fused launch
+        (cov_explore_expert): the streams live on the device, n_robots <= 624 (one key
+        regeneration per step) and the per-node greedy lists exist (max_nodes - n_robots <=
+        1024)."""
+        return self.hide_nodes and self._dev_streams and self._rngs is None and self.n_robots <= 624 and self.h.t_max <= 1024
+
     def _host_rngs(self):
         """The envs' np_random streams as host RandomStates (read back from the device the
         first time; the host keeps them from then on, until the next reset)."""
@@ -377,10 +384,14 @@ class VecCoverage:
         (controller(greedy=True), coverage.py:800-872, computed in the step's own launch).
         fallback: robots the reference hands to np_random.choice(4) (:861-864) draw it from
         their env's stream ("draw", the reference's semantics: on the device inside the
-        step when _device_draws(), else the greedy kernel, the draws on the host in robot
-        order and a resident step) or take action 0 ("zero"); include/gymflock.h
-        COV_ACTIONS_GREEDY, COV_GREEDY_RNG."""
+        step when _device_draws(), or with hidden nodes when _explore_fused(); else the
+        greedy kernel, the draws on the host in robot order and a resident step) or take
+        action 0 ("zero"); include/gymflock.h COV_ACTIONS_GREEDY, COV_GREEDY_RNG,
+        cov_explore_expert."""
         if resident or greedy:
+            if greedy and fallback == "draw" and self._explore_fused():
+                self.h.explore_expert(1, fetch=False)  # the masked expert, its draws, the step and the discovery
+                return
             if greedy and fallback == "draw" and not self._device_draws():
                 a, rnd = self.h.controller_greedy()
                 if rnd.any():
@@ -416,6 +427,29 @@ class VecCoverage:
             raise RuntimeError("expert_steps needs the envs' np_random streams on the device, n_robots <= 624 "
                                "and max_nodes - n_robots <= 1024")
         return self.h.step_expert(n_steps, fetch=fetch)
+
+    def explore_expert_steps(self, n_steps, record=("rewards", "done"), every=1, fetch=True, device_ptrs=None):
+        """n_steps of the reference's greedy expert on envs that hide nodes (ExploreEnv:
+        controller(greedy=True) masks visited or undiscovered targets and draws
+        np_random.choice(4) where it gives up, then step and the discovery) for every env in
+        ONE launch (cov_explore_expert): the same states, observations, rewards and streams as
+        n_steps calls of step(greedy=True). record: names among rewards, done, actions,
+        needs_random (every step's) and flat_obs (the hidden flat row after every `every`-th
+        step, float32); returns a dict of host arrays (done as bool). device_ptrs: {name:
+        device address} of caller-owned buffers (h.rollout_shapes(n_steps, every)), written
+        in stream order; returns None, as with fetch=False."""
+        if not self.hide_nodes:
+            raise RuntimeError("explore_expert_steps is for envs that hide nodes (hide_nodes=True); "
+                               "expert_steps is the form for the others")
+        if not (self._dev_streams and self._rngs is None):
+            raise RuntimeError("explore_expert_steps needs the envs' np_random streams on the device (a reset with "
+                               "draws=\"device\", or host draws with n_robots <= 624, and no host-drawn step since)")
+        out = self.h.explore_expert(n_steps, record, every, fetch, device_ptrs)
+        if out is not None:
+            for k in ("done", "needs_random"):
+                if k in out:
+                    out[k] = out[k].astype(bool)
+        return out
 
     def set_actions(self, actions):
         self.h.set_actions(actions)

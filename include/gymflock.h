@@ -721,6 +721,7 @@ int cov_get_graphs_tuple(cov_handle* h, int32_t* n_node, float* nodes, int32_t* 
  *     and drops the slots whose hidden sender is -1 (graph 0 only, or all: COV_MASK_ALL),
  *   - the fused expert forms (COV_ACTIONS_GREEDY, COV_NEXT_GREEDY, cov_step_expert,
  *     cov_step_host) return GF_EINVAL: they read the visited flags inside the step.
+ *     cov_explore_expert (below) is the fused expert form for such a handle.
  * enable = 0 turns the pass off again. A handle that never enables it launches and
  * allocates nothing for it. */
 int cov_set_hidden(cov_handle* h, int enable);
@@ -728,6 +729,42 @@ int cov_set_hidden(cov_handle* h, int enable);
  * i32, discovered (max_nodes) u8. Any pointer may be NULL. Edges, receivers and step are
  * cov_get_obs'. GF_ESTATE when the handle does not hide nodes. */
 int cov_get_hidden_obs(cov_handle* h, int env, float* nodes4, int32_t* senders, uint8_t* discovered);
+/* Expert rollouts of a handle that hides nodes (ExploreEnv), recorded: n_steps of
+ *   controller(greedy=True) with hide_nodes (the expert masks visited OR undiscovered targets,
+ *   its np_random.choice(4) fallback draws from the env's device stream, coverage.py:800-872),
+ *   step (:174-364), and the discovery from the robots' new positions (:334-346)
+ * in ONE launch, each env's workgroup stepping its env n_steps times with the discovered set
+ * in LDS. Afterwards the handle is exactly as after n_steps times (cov_controller_greedy,
+ * the fallback robots' draws in robot order, cov_set_actions, cov_step(COV_ACTIONS_RESIDENT)):
+ * every getter, the streams (cov_get_rng) and every later call see the same bits. The full
+ * hidden observation (node rows, frontier flags, hidden senders) is only rewritten after the
+ * last step and after the steps whose flat row is recorded.
+ * Records (any pointer may be NULL; rec may be NULL): */
+typedef struct cov_rollout {
+  double*  rewards;       /* (n_steps,B)   every step's                                   */
+  uint8_t* done;          /* (n_steps,B)                                                  */
+  int32_t* actions;       /* (n_steps,B,R) the expert's actions, fallback draws included  */
+  uint8_t* needs_random;  /* (n_steps,B,R) 1 where the action was drawn                   */
+  float*   flat_obs;      /* (K,B,16*max_nodes+1) hidden FlattenDictWrapper row after step t,
+                             for every t with (t+1) % record_every == 0                   */
+  int32_t  record_every;  /* >= 1 and divides n_steps; K = n_steps / record_every         */
+  int32_t  flags;         /* COV_ROLLOUT_DEVICE: pointers are caller-owned device memory  */
+} cov_rollout;
+#define COV_ROLLOUT_DEVICE 0x1
+/* Pairing for imitation learning: the row recorded after step t is the observation the expert
+ * saw when it chose actions[t + 1]; the observation for actions[0] is cov_get_flat_obs (with
+ * COV_FLAT_F32) before the call. With rec == NULL or COV_ROLLOUT_DEVICE the call only
+ * enqueues (device destinations are written by the kernel in stream order; cov_sync before
+ * reading them); host destinations go through the handle's scratch and the call returns when
+ * they are in place. Before any device work: GF_ESTATE when the handle does not hide nodes,
+ * has not been reset or has no device streams (cov_set_rng / cov_reset_seeded); GF_EINVAL
+ * for n_steps < 1, record_every < 1 or not a divisor of n_steps, unknown flags, n_robots >
+ * 624, more LDS than 64 KB per workgroup (cov_explore_lds_bytes), or max_nodes - n_robots >
+ * 1024 (the greedy lists, as for the other fused forms). */
+int cov_explore_expert(cov_handle* h, int n_steps, const cov_rollout* rec /* or NULL */);
+/* The LDS bytes a workgroup of cov_explore_expert takes for n_robots and max_nodes: the step's
+ * region, the hidden pass's and 16 bytes per target (host arithmetic only, no device). */
+int64_t cov_explore_lds_bytes(int n_robots, int max_nodes);
 
 /* Graph helpers of gym_flock/envs/spatial/utils.py ------
  * A context owns device scratch and the last edge list. Positions are host float64
