@@ -1,6 +1,8 @@
-// Plumbing shared by the C-ABI files (capi.hip, flock_comm.hip, cov_capi.hip, shepherd.hip,
-// graph_utils.hip): the error report, the HIP status check, typed device allocation and
-// the opening of every *_create. The helpers are static: none becomes a symbol of the library.
+// Plumbing shared by the C-ABI files (capi.hip, flock_comm.hip, cov_capi.hip,
+// cov_maps_capi.hip, cov_step_capi.hip, shepherd.hip, graph_utils.hip): the error report,
+// the HIP status checks, typed device allocation, the owner of a handle's device buffers
+// and the opening of every *_create. The helpers are static or hidden: none becomes a
+// symbol of the library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +31,13 @@ static inline int fail_hip(const char* what, hipError_t e) {
     if (e_ != hipSuccess) return gf::fail_hip(#expr, e_);   \
   } while (0)
 
+// The same for a kernel launch, named `what` ("<what>: <hipGetErrorString>").
+#define GF_LAUNCH(what, expr)                                    \
+  do {                                                           \
+    hipError_t e_ = (expr);                                      \
+    if (e_ != hipSuccess) return gf::fail_hip(what, e_);         \
+  } while (0)
+
 // `count` elements of device memory (device_alloc.h; count 0: nullptr).
 template <class T>
 static int dalloc(T** p, size_t count) {
@@ -50,6 +59,62 @@ static int dalloc_zero(T** p, size_t count) {
   GF_HIP(hipDeviceSynchronize());
   return GF_OK;
 }
+
+// The owner of a handle's device memory: what it hands out stays on its list until
+// free_one or free_all, so a handle's release names no buffer. Hidden, like the static
+// helpers above: no member becomes a symbol of the library.
+#pragma GCC visibility push(hidden)
+struct DeviceBuffers {
+  static constexpr int kMax = 128;  // a handle's pointer fields, each on the list at most once
+  void* ptrs[kMax];
+  int n = 0;
+
+  // dalloc_zero, remembered (also when the fill failed: free_all returns the memory).
+  template <class T>
+  int zeroed(T** p, size_t count) {
+    if (n == kMax) return fail(GF_ENOMEM, "device buffer list full");
+    const int rc = dalloc_zero(p, count);
+    if (*p) ptrs[n++] = *p;
+    return rc;
+  }
+  // `bytes` of hipMalloc, not filled, remembered.
+  template <class T>
+  hipError_t plain(T** p, size_t bytes) {
+    *p = nullptr;
+    if (n == kMax) return hipErrorOutOfMemory;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes);
+    if (e == hipSuccess) ptrs[n++] = *p;
+    return e;
+  }
+  // Frees *p and forgets it.
+  template <class T>
+  hipError_t free_one(T** p) {
+    if (!*p) return hipSuccess;
+    for (int k = 0; k < n; ++k)
+      if (ptrs[k] == *p) {
+        ptrs[k] = ptrs[--n];
+        break;
+      }
+    const hipError_t e = hipFree(*p);
+    *p = nullptr;
+    return e;
+  }
+  // The buffers that are reallocated when they must grow: *p holds at least `need`
+  // zero-filled elements, *have of them before the call.
+  template <class T>
+  int grow_zeroed(T** p, size_t* have, size_t need) {
+    if (need <= *have) return GF_OK;
+    GF_HIP(free_one(p));
+    *have = 0;
+    if (int rc = zeroed(p, need)) return rc;
+    *have = need;
+    return GF_OK;
+  }
+  void free_all() {
+    while (n > 0) hipFree(ptrs[--n]);
+  }
+};
+#pragma GCC visibility pop
 
 // The opening of every *_create: a device exists, `device` names one, and it becomes the
 // calling thread's current device.

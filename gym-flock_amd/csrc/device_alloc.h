@@ -1,4 +1,4 @@
-// Device buffer allocation shared by the C-ABI files (capi.hip, cov_capi.hip).
+// Device buffer allocation shared by the C-ABI files (capi.hip and, through capi_common.h, the cov_*_capi.hip files).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -307,6 +307,51 @@ static void coverage_session() {
     CHECK(fe_host_free(pin) == 0);
   }
   CHECK(cov_sync(h) == 0);
+  // the buffers allocated on first use, and those freed and reallocated when they grow, all
+  // on this handle before it is destroyed: device resets, hidden nodes, the hidden expert
+  // rollout (a longer one regrows the scratch), new maps (a second spacing rebuilds the
+  // lattice), and a reset that draws the next maps itself
+  std::vector<int32_t> st0((size_t)B * R), stat(B), nt(B), mst(B);
+  std::vector<uint8_t> vi0((size_t)B * (M - R)), rg0((size_t)B * (M - R));
+  CHECK(cov_reset_seeded(h, 5, 0.5, st0.data(), vi0.data()) == 0);
+  CHECK(cov_set_hidden(h, 1) == 0);
+  const size_t L = (size_t)16 * M + 1;
+  std::vector<double> xr_((size_t)4 * B);
+  std::vector<uint8_t> xd((size_t)4 * B), xn((size_t)4 * B * R);
+  std::vector<int32_t> xa((size_t)4 * B * R);
+  std::vector<float> xf((size_t)4 * B * L);
+  cov_rollout rec{};
+  rec.rewards = xr_.data();
+  rec.done = xd.data();
+  rec.actions = xa.data();
+  rec.needs_random = xn.data();
+  rec.flat_obs = xf.data();
+  rec.record_every = 1;
+  CHECK(cov_explore_expert(h, 2, &rec) == 0);
+  CHECK(cov_explore_expert(h, 4, &rec) == 0);
+  CHECK(cov_explore_expert(h, 3, nullptr) == 0);
+  cov_reset_config rc{};
+  rc.frac_active = 0.5;
+  const uint8_t mask[B] = {1, 0};
+  int32_t n_reset = -1;
+  CHECK(cov_reset_device(h, &rc, mask, st0.data(), vi0.data(), rg0.data(), stat.data(), &n_reset) == 0 && n_reset == 1);
+  cov_map_config mc{};
+  mc.x_min = mc.y_min = -20.0;
+  mc.x_max = mc.y_max = 20.0;
+  mc.lattice_spacing = 5.5;
+  mc.world_radius = 20.0;
+  mc.road_radius = mc.link_radius = 6.6;
+  mc.near_radius = 6.6 / 1.4;
+  mc.n_cities = 12;
+  CHECK(cov_generate_maps(h, &mc, -1, 8, nullptr, COV_MAP_SEED, nt.data(), mst.data(), nullptr) == 0);
+  mc.lattice_spacing = 5.0;  // still at most 4 targets within the motion radius of one
+  CHECK(cov_generate_maps(h, &mc, -1, 8, nullptr, COV_MAP_SEED, nt.data(), mst.data(), nullptr) == 0);
+  for (int b = 0; b < B; ++b) CHECK(nt[b] >= R && nt[b] <= M - R);
+  rc.flags = COV_RESET_SEED | COV_RESET_NEW_MAPS;
+  rc.seed = 3;
+  CHECK(cov_reset_device(h, &rc, nullptr, st0.data(), vi0.data(), rg0.data(), stat.data(), &n_reset) == 0 && n_reset == B);
+  CHECK(cov_explore_expert(h, 2, &rec) == 0);
+  CHECK(cov_set_hidden(h, 0) == 0);
   CHECK(cov_destroy(h) == 0);
 }
 
