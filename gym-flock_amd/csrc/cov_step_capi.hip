@@ -1,5 +1,5 @@
 // C-ABI of the Coverage-v0 engine, what moves the envs (include/gymflock.h): the time
-// matrices and greedy lists, the three resets, cov_step, cov_step_host, the two expert
+// matrices and greedy lists, the three resets, cov_step, cov_step_host, the three expert
 // rollouts and cov_controller_greedy.
 #include <algorithm>
 #include <cstring>
@@ -756,6 +756,92 @@ int cov_explore_expert(cov_handle* h, int n_steps, const cov_rollout* rec) {
   h->other_work = true;
   bool fetched = false;
   for (int k = 0; k < 5; ++k)
+    if (bytes[k]) {
+      if (int rc = copy_out(h, dst[k], out[k], bytes[k])) return rc;
+      fetched = true;
+    }
+  if (!fetched) return GF_OK;
+  GF_HIP(hipStreamSynchronize(h->stream));
+  return check_err(h);
+}
+
+int64_t cov_rollout_lds_bytes(int n_robots, int max_nodes, int auto_reset) {
+  if (n_robots < 1 || max_nodes < n_robots) return -1;
+  return (int64_t)gf::cov_rollout_lds_layout(n_robots, max_nodes, auto_reset != 0, nullptr);
+}
+
+// n_steps fused greedy expert steps with the device fallback draws in one launch, recorded
+// (cov_rollout_kernel); with ar, an env whose step sets done is reset inside the launch as
+// cov_reset_device(h, {frac_active, nearby, COV_RESET_DONE, 0}, NULL, ...) would reset it.
+int cov_expert_rollout(cov_handle* h, int n_steps, const cov_rollout* rec, const cov_auto_reset* ar) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_state) return fail(GF_ESTATE, "reset first (cov_reset)");
+  if (h->hidden) return fail(GF_EINVAL, std::string("cov_expert_rollout: ") + kHiddenFused);
+  if (!h->mt_key) return fail(GF_ESTATE, "set the envs' np_random streams first (cov_set_rng or cov_reset_seeded)");
+  if (n_steps < 1) return fail(GF_EINVAL, "n_steps must be at least 1");
+  const int every = rec ? rec->record_every : 1;
+  if (every < 1 || n_steps % every != 0) return fail(GF_EINVAL, "record_every must be at least 1 and divide n_steps");
+  if (rec && (rec->flags & ~COV_ROLLOUT_DEVICE)) return fail(GF_EINVAL, "unknown cov_rollout flags");
+  if (ar && ar->flags != 0) return fail(GF_EINVAL, "cov_auto_reset flags must be 0 (no seeding, no new maps inside a launch)");
+  if (ar && !(ar->frac_active >= 0.0 && ar->frac_active <= 1.0)) return fail(GF_EINVAL, "frac_active must be in [0, 1]");
+  if (ar && ar->nearby < 0) return fail(GF_EINVAL, "nearby must be >= 0");
+  const int R = h->cfg.n_robots, M = h->cfg.max_nodes;
+  if (R > gf::kMtN) return fail(GF_EINVAL, "n_robots <= 624 (one key regeneration per step)");
+  const char* need_lists = "the fused expert needs max_nodes - n_robots <= 1024 (the greedy lists)";
+  if (M - R > gf::kGreedyListMaxT) return fail(GF_EINVAL, need_lists);
+  const size_t lds = gf::cov_rollout_lds_layout(R, M, ar != nullptr, nullptr);
+  if (lds > gf::kCovRolloutLdsMax)
+    return fail(GF_EINVAL, "cov_expert_rollout: " + std::to_string(lds) + " bytes of LDS per workgroup exceed 64 KB (cov_rollout_lds_bytes)");
+  if (int rc = use(h)) return rc;
+  if (int rc = ensure_greedy_lists(h, need_lists)) return rc;
+  if (int rc = join_s2(h)) return rc;
+  gf::CovArgsR x{};
+  x.a = h->a;
+  x.a.actions = nullptr;
+  greedy_args(h, x.a, true);
+  x.n_steps = n_steps;
+  x.record_every = every;
+  x.auto_reset = ar ? 1 : 0;
+  if (ar) {
+    x.d.R = R;
+    x.d.Tmax = h->a.Tmax;
+    x.d.nearby = ar->nearby;
+    x.d.frac = ar->frac_active;
+    x.d.ntg = h->ntg;
+    x.d.nbr = h->a.nbr;
+    x.d.cnt = h->a.cnt;
+    x.d.mt_key = h->mt_key;
+    x.d.mt_pos = h->mt_pos;
+    x.d.start = h->start;
+    x.d.visited0 = h->visited0;
+  }
+  const size_t B = h->cfg.n_envs, n = (size_t)n_steps * B, K = (size_t)(n_steps / every);
+  const size_t L = (size_t)15 * M + 1;
+  // device destinations are written in place; host ones go through the scratch
+  const bool device = rec && (rec->flags & COV_ROLLOUT_DEVICE);
+  const cov_rollout none{};
+  const cov_rollout& r = rec ? *rec : none;
+  void* dst[7] = {r.rewards, r.done, r.actions, r.needs_random, r.flat_obs, ar ? ar->n_resets : nullptr,
+                  ar ? ar->status : nullptr};
+  const size_t want[7] = {n * 8, n, n * R * 4, n * R, K * B * L * 4, B * 4, B * 4};
+  size_t bytes[7];
+  for (int k = 0; k < 7; ++k) bytes[k] = !device && dst[k] ? want[k] : 0;
+  unsigned char* out[7];
+  if (int rc = gf::scratch_records(h, 7, bytes, out)) return rc;
+  if (device)
+    for (int k = 0; k < 7; ++k) out[k] = static_cast<unsigned char*>(dst[k]);
+  x.reward_k = reinterpret_cast<double*>(out[0]);
+  x.done_k = out[1];
+  x.act_k = reinterpret_cast<int32_t*>(out[2]);
+  x.nrand_k = out[3];
+  x.flat_k = reinterpret_cast<float*>(out[4]);
+  x.n_resets = reinterpret_cast<int32_t*>(out[5]);
+  x.status = reinterpret_cast<int32_t*>(out[6]);
+  GF_LAUNCH("cov_rollout_kernel", gf::launch_cov_rollout(x, h->stream));
+  h->main_dirty = true;
+  h->other_work = true;
+  bool fetched = false;
+  for (int k = 0; k < 7; ++k)
     if (bytes[k]) {
       if (int rc = copy_out(h, dst[k], out[k], bytes[k])) return rc;
       fetched = true;

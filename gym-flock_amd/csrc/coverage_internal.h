@@ -199,14 +199,16 @@ __device__ __forceinline__ void greedy_direct_list(const uint32_t* vbits, int T,
 // consumed in stream order by a register chain (readlane; the masked rejection of each i),
 // the accepted ones into vseq[i]; then lane 0 runs the swaps, one LDS round trip each (the
 // draws and swaps interleaved waited on two per swap; profiles/r06/ab_seed_reset_draws.txt).
-// perm and vseq hold n words each. Every lane of the wave calls it.
+// perm and vseq hold n words each. Every lane of the wave calls it. Sync: mt19937.h.
+template <class Sync = WgSync>
 __device__ __forceinline__ void cov_permute(uint32_t* key, int& pos, int32_t* perm, int32_t* vseq, int n) {
+  const Sync sync;
   const int lane = threadIdx.x;
   for (int k = lane; k < n; k += 64) perm[k] = k;
   int i = n - 1;  // wave-uniform
   while (i >= 1) {
     if (pos == kMtN) {
-      mt_regen<64>(key);
+      mt_regen<64, Sync>(key);
       pos = 0;
     }
     const int avail = min(64, kMtN - pos);
@@ -222,7 +224,7 @@ __device__ __forceinline__ void cov_permute(uint32_t* key, int& pos, int32_t* pe
     }
     pos += u;
   }
-  __syncthreads();
+  sync();
   if (lane == 0 && n > 1) {  // one lane: its LDS reads and writes stay in program order
     // the next swap's draw is read with this swap's entries (vseq is not written here),
     // so a swap waits on one LDS round trip, not two
@@ -236,7 +238,7 @@ __device__ __forceinline__ void cov_permute(uint32_t* key, int& pos, int32_t* pe
       v = vnext;
     }
   }
-  __syncthreads();
+  sync();
 }
 
 // Shared by the map kernels (coverage_maps.hip, coverage_arl.hip): workgroup compaction
@@ -595,6 +597,32 @@ struct CovResetDrawArgs {
 constexpr int32_t kResetRegionShort = 1, kResetRegionSmall = 2;
 size_t cov_reset_draw_lds_bytes(int Tmax);
 hipError_t launch_cov_reset_draw(const CovResetDrawArgs& a, hipStream_t s);
+// cov_expert_rollout: n_steps fused greedy expert steps of envs that hide nothing in one
+// launch, recorded, with an env that finishes reset inside the launch (cov_rollout_kernel,
+// coverage_rollout.hip). a: the step's arguments with the greedy lists and the streams set.
+// d (auto_reset only): the draws' arguments; of them R, Tmax, nearby, frac, ntg, nbr, cnt,
+// mt_key, mt_pos, start and visited0 are used. Records (any may be nullptr): every step's
+// reward, done flag, actions and needs-random flags, and after every record_every-th step the
+// env's flat row (cov_flat_obs_kernel's, nf = 3, float32), the row after the reset where one
+// has just happened.
+struct CovArgsR {
+  CovArgs a;
+  CovResetDrawArgs d;
+  int n_steps, record_every, auto_reset;
+  int draw_off;           // cov_rollout_lds_layout's byte offset of the draws' LDS
+  double* reward_k;       // (n_steps,B)
+  uint8_t* done_k;        // (n_steps,B)
+  int32_t* act_k;         // (n_steps,B,R)
+  uint8_t* nrand_k;       // (n_steps,B,R)
+  float* flat_k;          // (n_steps / record_every,B,15M+1)
+  int32_t* n_resets;      // (B) resets of env b made by this launch
+  int32_t* status;        // (B) OR of their kResetRegion* bits
+};
+// The kernel's dynamic LDS: the step's region (cov_step_lds_bytes), then with auto_reset from
+// *draw_off the draws' (cov_reset_draw_lds_bytes). Returns the total.
+size_t cov_rollout_lds_layout(int R, int M, bool auto_reset, int* draw_off);
+constexpr size_t kCovRolloutLdsMax = 64 * 1024;
+hipError_t launch_cov_rollout(const CovArgsR& x, hipStream_t s);
 // reset()'s random draws on the device for envs seeded seed0 + b (start (B,R), visited0
 // (B,Tmax)), the streams left in a.mt_key / a.mt_pos
 hipError_t launch_cov_seed_reset(const CovArgs& a, uint32_t seed0, double frac, int32_t* start, uint8_t* visited0,

@@ -74,14 +74,20 @@ class CovRollout(ctypes.Structure):
 COV_ROLLOUT_DEVICE = 0x1  # cov_rollout flag: the record pointers are device memory
 
 
-def cov_rollout_shapes(n_steps, n_envs, n_robots, max_nodes, every=1):
-    """name -> (shape, dtype) of cov_explore_expert's records (cov_rollout): every step's
-    rewards, done, actions and needs_random, and the hidden flat rows (16 * max_nodes + 1
-    wide, float32) after every `every`-th step."""
+class CovAutoReset(ctypes.Structure):
+    _fields_ = [("frac_active", ctypes.c_double), ("nearby", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("n_resets", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+def cov_rollout_shapes(n_steps, n_envs, n_robots, max_nodes, every=1, hidden=True):
+    """name -> (shape, dtype) of the records (cov_rollout) of cov_explore_expert (hidden: the
+    hidden flat rows, 16 * max_nodes + 1 wide) and cov_expert_rollout (hidden=False: 15 *
+    max_nodes + 1 wide): every step's rewards, done, actions and needs_random, and the float32
+    flat rows after every `every`-th step."""
     k, b, r = n_steps // every, n_envs, n_robots
     return {"rewards": ((n_steps, b), np.float64), "done": ((n_steps, b), np.uint8),
             "actions": ((n_steps, b, r), np.int32), "needs_random": ((n_steps, b, r), np.uint8),
-            "flat_obs": ((k, b, 16 * max_nodes + 1), np.float32)}
+            "flat_obs": ((k, b, (16 if hidden else 15) * max_nodes + 1), np.float32)}
 
 
 class FeResetConfig(ctypes.Structure):
@@ -295,6 +301,8 @@ SIGNATURES = {
     "cov_get_hidden_obs": [_P, _I, _P, _P, _P],
     "cov_explore_expert": [_P, _I, ctypes.POINTER(CovRollout)],
     "cov_explore_lds_bytes": [_I, _I],
+    "cov_expert_rollout": [_P, _I, ctypes.POINTER(CovRollout), ctypes.POINTER(CovAutoReset)],
+    "cov_rollout_lds_bytes": [_I, _I, _I],
     "gu_create": [_I, ctypes.POINTER(_P)],
     "gu_destroy": [_P],
     "gu_radius_edges": [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_double, _I,
@@ -323,7 +331,8 @@ SIGNATURES = {
     "fe_kernel_timing": [_P, _I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)],
     "cov_kernel_timing": [_P, _I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)],
 }
-_RESTYPE = {"fe_last_error": ctypes.c_char_p, "cov_explore_lds_bytes": ctypes.c_int64}
+_RESTYPE = {"fe_last_error": ctypes.c_char_p, "cov_explore_lds_bytes": ctypes.c_int64,
+            "cov_rollout_lds_bytes": ctypes.c_int64}
 
 _lib = None
 
@@ -1162,8 +1171,65 @@ class CoverageHandle:
         return (r, d.astype(bool)) if fetch else None
 
     def rollout_shapes(self, n_steps, every=1):
-        """name -> (shape, dtype) of cov_explore_expert's records (cov_rollout)."""
-        return cov_rollout_shapes(n_steps, self.n_envs, self.n_robots, self.max_nodes, every)
+        """name -> (shape, dtype) of the records (cov_rollout) of explore_expert (a handle with
+        set_hidden: flat rows 16 * max_nodes + 1 wide) or expert_rollout (15 * max_nodes + 1)."""
+        return cov_rollout_shapes(n_steps, self.n_envs, self.n_robots, self.max_nodes, every,
+                                  hidden=self.n_node_feat == 4)
+
+    def expert_rollout(self, n_steps, record=(), every=1, fetch=True, device_ptrs=None, auto_reset=None):
+        """n_steps fused greedy expert steps with the device fallback draws in one launch,
+        recorded (cov_expert_rollout), on a handle that does not hide nodes: the state
+        afterwards is that of n_steps step(greedy=True, rng=True) calls. record: names among
+        rewards, done, actions, needs_random (every step's) and flat_obs (the flat float32 row
+        after every `every`-th step; `every` divides n_steps); shapes in rollout_shapes().
+        auto_reset: None (an env steps on past done), or (frac_active, nearby) / a dict with
+        those keys: an env whose step sets done is reset inside the launch from its own stream,
+        as reset_device(done=True, frac_active=..., nearby=...) after that step would reset
+        it; an env whose start region has fewer nodes than robots keeps stepping with
+        COV_RESET_REGION_SMALL in its status. Returns a dict of host arrays (with auto_reset
+        also n_resets (B) and reset_status (B)) and waits for them. device_ptrs: {name: device
+        address} of caller-owned buffers of those shapes (with auto_reset also n_resets /
+        reset_status, (B) int32), written in stream order instead (only enqueues, returns
+        None; `record` is ignored). fetch=False (and no device_ptrs): nothing is recorded,
+        only enqueues, returns None. flat_obs[k] is what the expert saw when it chose
+        actions[(k + 1) * every], the reset observation after a step that set done;
+        flat_obs(f32=True) before the call is what it saw for actions[0]."""
+        n_steps, every = int(n_steps), int(every)
+        shapes = dict(self.rollout_shapes(max(n_steps, 0), max(every, 1)))
+        rec = CovRollout()
+        rec.record_every = every
+        ar = None
+        if auto_reset is not None:
+            if isinstance(auto_reset, dict):
+                frac, nearby = auto_reset["frac_active"], auto_reset.get("nearby", 0)
+            else:
+                frac, nearby = auto_reset
+            ar = CovAutoReset(float(frac), int(nearby), 0, None, None)
+            shapes["n_resets"] = shapes["reset_status"] = ((self.n_envs,), np.int32)
+        field = {"n_resets": "n_resets", "reset_status": "status"}
+
+        def put(name, addr):
+            if name not in shapes:
+                raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+            if name in field:
+                setattr(ar, field[name], ctypes.c_void_p(addr))
+            else:
+                setattr(rec, name, ctypes.c_void_p(addr))
+
+        out = None
+        if device_ptrs is not None:
+            for name, addr in device_ptrs.items():
+                put(name, int(addr))
+            rec.flags = COV_ROLLOUT_DEVICE
+        elif fetch:
+            out = {}
+            for name in tuple(record) + (("n_resets", "reset_status") if ar is not None else ()):
+                if name not in shapes:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+                out[name] = np.zeros(*shapes[name])
+                put(name, out[name].ctypes.data)
+        check(self.lib.cov_expert_rollout(self.h, n_steps, ctypes.byref(rec), ctypes.byref(ar) if ar is not None else None))
+        return out
 
     def explore_expert(self, n_steps, record=(), every=1, fetch=True, device_ptrs=None):
         """n_steps of the hidden-node expert (controller(greedy=True) with hide_nodes and its

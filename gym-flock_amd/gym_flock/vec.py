@@ -428,6 +428,41 @@ class VecCoverage:
                                "and max_nodes - n_robots <= 1024")
         return self.h.step_expert(n_steps, fetch=fetch)
 
+    def expert_rollout(self, n_steps, record=("rewards", "done"), every=1, auto_reset=False, nearby=None, fetch=True,
+                       device_ptrs=None):
+        """expert_steps with records, and across episode ends, in ONE launch
+        (cov_expert_rollout): the reference driver's loop `reset(); while not done: a =
+        controller(greedy=True); step(a)` for every env, its output the demonstrations.
+        record: names among rewards, done, actions, needs_random (every step's) and flat_obs
+        (the flat float32 row after every `every`-th step); returns a dict of host arrays
+        (done and needs_random as bool). auto_reset: an env whose step sets done is reset
+        inside the launch as reset_envs("done", nearby=nearby) right after that step would
+        reset it (same map, frac_active_targets of the constructor, nearby defaulting as in
+        reset_envs); the dict then also has n_resets (B) and reset_status (B), and flat_obs
+        after a done step is the reset observation (the terminal one is not recorded). An env
+        whose start region has fewer nodes than robots is not reset and goes on stepping
+        (COV_RESET_REGION_SMALL in reset_status). device_ptrs: {name: device address} of
+        caller-owned buffers (h.rollout_shapes(n_steps, every); n_resets / reset_status (B)
+        int32), written in stream order; returns None, as with fetch=False. The preconditions
+        are expert_steps's; refused with hide_nodes (explore_expert_steps is the form there)."""
+        if self.hide_nodes:
+            raise RuntimeError("expert_rollout is for envs that do not hide nodes; explore_expert_steps is the "
+                               "form for hide_nodes=True")
+        if not self._device_draws():
+            raise RuntimeError("expert_steps needs the envs' np_random streams on the device, n_robots <= 624 "
+                               "and max_nodes - n_robots <= 1024")
+        ar = None
+        if auto_reset:
+            if nearby is None:
+                nearby = self.n_robots * 5 if self.nearby_starts else 0
+            ar = (self.frac, int(nearby))
+        out = self.h.expert_rollout(n_steps, record, every, fetch, device_ptrs, auto_reset=ar)
+        if out is not None:
+            for k in ("done", "needs_random"):
+                if k in out:
+                    out[k] = out[k].astype(bool)
+        return out
+
     def explore_expert_steps(self, n_steps, record=("rewards", "done"), every=1, fetch=True, device_ptrs=None):
         """n_steps of the reference's greedy expert on envs that hide nodes (ExploreEnv:
         controller(greedy=True) masks visited or undiscovered targets and draws

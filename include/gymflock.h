@@ -746,7 +746,9 @@ typedef struct cov_rollout {
   int32_t* actions;       /* (n_steps,B,R) the expert's actions, fallback draws included  */
   uint8_t* needs_random;  /* (n_steps,B,R) 1 where the action was drawn                   */
   float*   flat_obs;      /* (K,B,16*max_nodes+1) hidden FlattenDictWrapper row after step t,
-                             for every t with (t+1) % record_every == 0                   */
+                             for every t with (t+1) % record_every == 0. On a handle that
+                             does not hide nodes (cov_expert_rollout) the row is
+                             15*max_nodes+1 wide.                                         */
   int32_t  record_every;  /* >= 1 and divides n_steps; K = n_steps / record_every         */
   int32_t  flags;         /* COV_ROLLOUT_DEVICE: pointers are caller-owned device memory  */
 } cov_rollout;
@@ -765,6 +767,52 @@ int cov_explore_expert(cov_handle* h, int n_steps, const cov_rollout* rec /* or 
 /* The LDS bytes a workgroup of cov_explore_expert takes for n_robots and max_nodes: the step's
  * region, the hidden pass's and 16 bytes per target (host arithmetic only, no device). */
 int64_t cov_explore_lds_bytes(int n_robots, int max_nodes);
+
+/* n_steps greedy expert steps of a handle that does NOT hide nodes in one launch, recorded,
+ * across episode ends: the reference driver's loop `reset(); while not done: a =
+ * controller(greedy=True); step(a)` for every env of the batch, its output the demonstrations
+ * for imitation learning. Records: cov_rollout (above), rows 15 * max_nodes + 1 wide.
+ *
+ * Without ar the handle afterwards is exactly as after n_steps calls of cov_step(h, NULL,
+ * COV_ACTIONS_GREEDY | COV_GREEDY_RNG): rewards and done equal cov_step_expert's, and every
+ * getter, cov_get_rng and every later call see the same bits; an env steps on past done.
+ *
+ * With ar an env is reset inside the launch right after a step of this call sets its done
+ * flag, on its unchanged map (coverage.py:398-424 with graph_changed == False), drawing from
+ * its own np_random stream where the step left it: the handle afterwards is exactly as after
+ * n_steps rounds of that step, each followed by cov_reset_device(h, {frac_active, nearby,
+ * COV_RESET_DONE, 0}, NULL, ...) whose GF_EINVAL for a too-small region is ignored. An env
+ * that is already done on entry is simply stepped. An env whose start region has fewer nodes
+ * than robots (COV_RESET_REGION_SMALL) keeps its state, has its stream advanced by the scalar
+ * draw, gets the bit in status[b] and goes on stepping; it is not counted in n_resets[b], and
+ * the call still returns GF_OK (a call that only enqueues cannot fail late). */
+typedef struct {
+  double   frac_active;  /* as cov_reset_config */
+  int32_t  nearby;       /* as cov_reset_config */
+  int32_t  flags;        /* must be 0: no seeding, no new maps inside a launch */
+  int32_t* n_resets;     /* (B) resets of env b made by this call, or NULL */
+  int32_t* status;       /* (B) OR of the COV_RESET_REGION_* bits of those resets, or NULL */
+} cov_auto_reset;
+/* Pairing for imitation learning: the row recorded after step t is the observation the expert
+ * saw when it chose actions[t + 1]; after a step that set done it is the reset observation, so
+ * done[t] marks the last step of an episode, rewards[t] is that step's reward, and the
+ * terminal observation is not recorded. The observation for actions[0] is cov_get_flat_obs
+ * (with COV_FLAT_F32) before the call. COV_ROLLOUT_DEVICE in rec->flags also governs
+ * ar->n_resets and ar->status. With rec == NULL (and no host destination in ar) or
+ * COV_ROLLOUT_DEVICE the call only enqueues; host destinations go through the handle's
+ * scratch and the call returns when they are in place. Before any device work: GF_ESTATE
+ * when the handle has not been reset or has no device streams (cov_set_rng /
+ * cov_reset_seeded); GF_EINVAL for a handle that hides nodes (cov_explore_expert is its
+ * form), n_steps < 1, record_every < 1 or not a divisor of n_steps, unknown rec->flags,
+ * ar->flags != 0, frac_active outside [0,1], nearby < 0, n_robots > 624, max_nodes -
+ * n_robots > 1024 (the greedy lists), or more LDS than 64 KB per workgroup
+ * (cov_rollout_lds_bytes). */
+int cov_expert_rollout(cov_handle* h, int n_steps, const cov_rollout* rec /* or NULL */,
+                       const cov_auto_reset* ar /* NULL: no reset, envs step on past done */);
+/* The LDS bytes a workgroup of cov_expert_rollout takes: the step's region and, with
+ * auto_reset, the reset draws' (key, permutation, draws, two bit sets, flags). Host
+ * arithmetic only, no device. */
+int64_t cov_rollout_lds_bytes(int n_robots, int max_nodes, int auto_reset);
 
 /* Graph helpers of gym_flock/envs/spatial/utils.py ------
  * A context owns device scratch and the last edge list. Positions are host float64
