@@ -38,9 +38,10 @@ struct WaveSync {
 // passes of at most 227 independent words each, then word 623: [0,227) reads only old
 // words, [227,454) reads the first pass's results, [454,623) the second's. Ends with a
 // barrier. Every thread of the workgroup calls it (Sync = WaveSync: every lane of the one
-// wave, NT = 64).
+// wave, NT = 64). tid: the caller's index among the NT threads that share the work; a
+// thread beyond them passes kMtN and only keeps the barriers.
 template <int NT, class Sync = WgSync>
-__device__ __forceinline__ void mt_regen(uint32_t* k) {
+__device__ __forceinline__ void mt_regen(uint32_t* k, const int tid = static_cast<int>(threadIdx.x)) {
   const Sync sync;
   constexpr int P = kMtN - kMtM;  // 227
   constexpr int S = (P + NT - 1) / NT;
@@ -48,13 +49,13 @@ __device__ __forceinline__ void mt_regen(uint32_t* k) {
     uint32_t v[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-      const int i = lo + static_cast<int>(threadIdx.x) + s * NT;
+      const int i = lo + tid + s * NT;
       if (i < hi) v[s] = mt_mix(k[i], k[i + 1], k[i < P ? i + kMtM : i - P]);
     }
     sync();
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-      const int i = lo + static_cast<int>(threadIdx.x) + s * NT;
+      const int i = lo + tid + s * NT;
       if (i < hi) k[i] = v[s];
     }
     sync();
@@ -62,7 +63,7 @@ __device__ __forceinline__ void mt_regen(uint32_t* k) {
   pass(0, P);
   pass(P, 2 * P);
   pass(2 * P, kMtN - 1);
-  if (threadIdx.x == 0) k[kMtN - 1] = mt_mix(k[kMtN - 1], k[0], k[kMtM - 1]);
+  if (tid == 0) k[kMtN - 1] = mt_mix(k[kMtN - 1], k[0], k[kMtM - 1]);
   sync();
 }
 

@@ -20,6 +20,16 @@
 // cos / sin / atan2 are the device library's; they are not NumPy's to the last bit, so
 // free-running trajectories match the reference to rounding. The adjacency, the reward
 // and the sheep controls contain no trigonometry and are bit-exact for the same state.
+//
+// The launch arguments, the handle and the line-of-sight test are shepherd_internal.h's,
+// shared with the reset and recorded-rollout kernels of shepherd_rollout.hip. That header
+// also holds this kernel's step as inline functions (controller_out, sheep_sum, unicycle,
+// reward_of, write_obs, write_adj), which those kernels call. shep_kernel keeps the step
+// written out below, statement for statement the same arithmetic: built from the
+// functions it had the same registers and five instructions fewer, yet measured 2 % slower
+// per step at 512 envs (9.74 against 9.53 us in 100-step launches, three alternating runs
+// each), so its text stays. tests/test_shepherding_rollout_gpu.py holds the two forms
+// equal bit for bit (a rollout against step(expert=True) and against expert_steps).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,43 +37,13 @@
 #include <string>
 
 #include "capi_common.h"
+#include "shepherd_internal.h"
 
 using gf::dalloc;
 using gf::fail;
+using namespace gf::shep;
 
 namespace {
-
-constexpr int kWaveEnvs = 4;      // envs per workgroup in the wave-per-env shape
-constexpr int kMaxAgents = 1024;  // one workgroup per env above 64 agents
-
-enum ShepMode { M_OBSERVE = 0, M_STEP = 1, M_CONTROLLER = 2, M_ROLLOUT = 3 };
-
-struct ShepArgs {
-  int B = 0, N = 0, nsh = 0;
-  int mode = 0, n_steps = 0;
-  int u_f64 = 0;             // the actions at u are float64 (else float32)
-  double dt = 0, comm_r2 = 0, action_scalar = 0;
-  double w_shep = 0, w_sheep = 0, goal_r = 0;
-  double los2 = 0, los5 = 0;  // np.deg2rad(2), np.deg2rad(5)
-  double* x = nullptr;        // (B,N,3)
-  double* obs = nullptr;      // (B,N,4)
-  double* adj = nullptr;      // (B,N,N)
-  double* rew = nullptr;      // (B)
-  double* ctrl = nullptr;     // (B,N,2) the control of the last step, all agents
-  const void* u = nullptr;    // (B,nsh,2) shepherd actions (M_STEP)
-  double* uout = nullptr;     // (B,nsh,2) controller output (M_CONTROLLER)
-  double* rew_steps = nullptr;  // (n_steps,B) or null (M_ROLLOUT)
-};
-
-// _wrapToPi :235-238 of atan2(v) - heading, against a threshold (:240-273)
-__device__ inline bool in_los(double xs, double ys, double ths, double xt, double yt, double thr) {
-  const double vx = xt - xs, vy = yt - ys;
-  const double a = atan2(vy, vx) - ths;
-  const double dth = a == 0.0 ? 0.0 : atan2(sin(a), cos(a));
-  return fabs(dth) < thr;
-}
-
-__device__ inline bool all_nonzero(double x, double y, double th) { return x != 0.0 && y != 0.0 && th != 0.0; }
 
 template <bool WAVE>
 __global__ __launch_bounds__(WAVE ? 64 * kWaveEnvs : kMaxAgents) void shep_kernel(ShepArgs a) {
@@ -233,23 +213,6 @@ __global__ __launch_bounds__(256) void shep_cast_kernel(const double* src, float
   for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) dst[k] = (float)src[k];
 }
 
-}  // namespace
-
-struct shep_handle {
-  shep_config cfg{};
-  hipStream_t stream = nullptr;
-  ShepArgs a{};
-  double* ubuf = nullptr;     // (B,nsh,2) doubles: the resident actions (float32 ones use half)
-  double* rew_steps = nullptr;
-  size_t rew_steps_cap = 0;   // in doubles
-  void* scratch = nullptr;    // float32 casts on their way to host memory
-  size_t scratch_cap = 0;
-  bool has_state = false, has_obs = false, has_ctrl = false, has_u = false;
-  int u_f64 = 0;              // dtype of the resident actions
-};
-
-namespace {
-
 int launch(shep_handle* h, int mode, int n_steps, double* rew_steps) {
   ShepArgs a = h->a;
   a.mode = mode;
@@ -340,6 +303,8 @@ int shep_create(const shep_config* cfg, shep_handle** out) {
     return rc;
   }
   a.uout = h->ubuf;
+  h->ep_count.assign((size_t)a.B, 0);
+  h->rng_set.assign((size_t)a.B, 0);
   *out = h;
   return GF_OK;
 }
@@ -348,7 +313,8 @@ int shep_destroy(shep_handle* h) {
   if (!h) return GF_OK;
   hipSetDevice(h->cfg.device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  void* bufs[] = {h->a.x, h->a.obs, h->a.ctrl, h->ubuf, h->rew_steps, h->scratch};
+  void* bufs[] = {h->a.x,  h->a.obs,  h->a.ctrl,    h->ubuf,     h->rew_steps, h->scratch,
+                  h->mt_key, h->mt_pos, h->count_dev, h->mask_dev, h->rec};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->stream) hipStreamDestroy(h->stream);
@@ -363,6 +329,7 @@ int shep_set_state(shep_handle* h, const double* x) {
   GF_HIP(hipStreamSynchronize(h->stream));
   h->has_state = true;
   h->has_obs = h->has_ctrl = false;
+  h->ep_count.assign(h->ep_count.size(), 0);
   return GF_OK;
 }
 
@@ -413,6 +380,7 @@ int shep_step(shep_handle* h, const void* u, int flags) {
   }
   if (int rc = launch(h, mode, 1, nullptr)) return rc;
   h->has_obs = h->has_ctrl = true;
+  h->count_steps(1);
   return GF_OK;
 }
 
@@ -446,6 +414,7 @@ int shep_step_expert(shep_handle* h, int n_steps, double* rewards) {
   }
   if (int rc = launch(h, M_ROLLOUT, n_steps, h->rew_steps)) return rc;
   h->has_obs = h->has_ctrl = true;
+  h->count_steps(n_steps);
   if (rewards) {
     GF_HIP(hipMemcpyAsync(rewards, h->rew_steps, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     GF_HIP(hipStreamSynchronize(h->stream));

@@ -194,6 +194,28 @@ SHEP_U_EXPERT = 0x08
 SHEP_U_RESIDENT = 0x80
 SHEP_OUT_DEVICE = 0x4
 SHEP_OUT_F32 = 0x8
+SHEP_RESET_SEED = 0x1
+SHEP_RESET_ZERO_HEADINGS = 0x2
+SHEP_REC_DEVICE = 0x4
+SHEP_REC_F32 = 0x8
+
+
+class ShepResetConfig(ctypes.Structure):
+    _fields_ = [("r_max", ctypes.c_double), ("goal_offset", ctypes.c_double * 2)]
+
+
+class ShepRolloutRecords(ctypes.Structure):
+    _fields_ = [("obs", ctypes.c_void_p), ("adj", ctypes.c_void_p), ("actions", ctypes.c_void_p),
+                ("rewards", ctypes.c_void_p), ("done", ctypes.c_void_p), ("n_resets", ctypes.c_void_p)]
+
+
+def shep_rollout_shapes(n_steps, n_envs, n_shepherds, n_agents, every=1, f32=False):
+    """name -> (shape, dtype) of shep_expert_rollout's records (shep_rollout_records)."""
+    k = n_steps // every
+    real = np.float32 if f32 else np.float64
+    return {"obs": ((k, n_envs, n_agents, 4), real), "adj": ((k, n_envs, n_agents, n_agents), real),
+            "actions": ((n_steps, n_envs, n_shepherds, 2), real), "rewards": ((n_steps, n_envs), np.float64),
+            "done": ((n_steps, n_envs), np.uint8), "n_resets": ((n_envs,), np.int32)}
 
 
 class GymFlockError(RuntimeError):
@@ -325,6 +347,11 @@ SIGNATURES = {
     "shep_get_outputs": [_P, _P],
     "shep_get_controls": [_P, _P],
     "shep_sync": [_P],
+    "shep_set_rng": [_P, _I, _P, _P],
+    "shep_get_rng": [_P, _I, _P, _P],
+    "shep_reset_device": [_P, ctypes.POINTER(ShepResetConfig), ctypes.c_uint64, _P, _I],
+    "shep_get_episode_steps": [_P, _P],
+    "shep_expert_rollout": [_P, _I, _I, _I, ctypes.POINTER(ShepResetConfig), ctypes.POINTER(ShepRolloutRecords), _I],
     "fe_last_error": [],
     "fe_abi_version": [],
     "fe_diag": [_P, _I, _I, ctypes.POINTER(ctypes.c_double)],
@@ -1564,6 +1591,103 @@ class ShepherdHandle:
 
     def sync(self):
         check(self.lib.shep_sync(self.h))
+
+    # -- streams, the reset on the device and recorded rollouts (csrc/shepherd_rollout.hip)
+    def set_rng(self, states, env=None):
+        """The envs' MT19937 streams: a list of B RandomState objects or get_state() tuples
+        (the legacy np.random state), or one with env=<b> (shep_set_rng)."""
+        if env is not None:
+            states = [states]
+        assert len(states) == (self.n_envs if env is None else 1)
+        keys = np.empty((len(states), 624), np.uint32)
+        pos = np.empty(len(states), np.int32)
+        for b, st in enumerate(states):
+            st = st.get_state() if hasattr(st, "get_state") else st
+            assert st[0] == "MT19937" and len(st[1]) == 624, "a legacy RandomState (MT19937) state"
+            keys[b], pos[b] = st[1], st[2]
+        check(self.lib.shep_set_rng(self.h, -1 if env is None else int(env), ptr(keys), ptr(pos)))
+
+    def get_rng(self, env=None):
+        """(keys (B,624) uint32, pos (B) int32) of every env's stream, or (keys (624), pos)
+        of one: RandomState.set_state(("MT19937", keys, pos)) continues it (shep_get_rng)."""
+        n = self.n_envs if env is None else 1
+        keys = np.empty((n, 624), np.uint32)
+        pos = np.empty(n, np.int32)
+        check(self.lib.shep_get_rng(self.h, -1 if env is None else int(env), ptr(keys), ptr(pos)))
+        return (keys, pos) if env is None else (keys[0], int(pos[0]))
+
+    def _mask(self, envs):
+        if envs is None:
+            return None
+        e = np.asarray(envs)
+        if e.dtype == np.bool_:
+            assert e.shape == (self.n_envs,), e.shape
+            return np.ascontiguousarray(e, dtype=np.uint8)
+        mask = np.zeros(self.n_envs, np.uint8)
+        mask[e.astype(np.int64)] = 1
+        return mask
+
+    def reset_device(self, r_max, goal_offset, seed=None, envs=None, zero_headings=False, flags=None):
+        """reset() (shepherding.py:187-202) of the selected envs in one launch
+        (shep_reset_device), each from its own stream: RandomState(seed + b) or, with seed
+        None, continued. envs: None (all), a bool mask (B) or a list of env indices.
+        Headings are kept unless zero_headings. flags: the raw flag word instead.
+        Asynchronous."""
+        rc = ShepResetConfig(float(r_max), (ctypes.c_double * 2)(float(goal_offset[0]), float(goal_offset[1])))
+        if flags is None:
+            flags = (0 if seed is None else SHEP_RESET_SEED) | (SHEP_RESET_ZERO_HEADINGS if zero_headings else 0)
+        check(self.lib.shep_reset_device(self.h, ctypes.byref(rc), int(seed or 0), ptr(self._mask(envs)), int(flags)))
+
+    def episode_steps(self):
+        """The envs' episode step counts (B) int32 (shep_get_episode_steps)."""
+        out = np.empty(self.n_envs, np.int32)
+        check(self.lib.shep_get_episode_steps(self.h, ptr(out)))
+        return out
+
+    def rollout_shapes(self, n_steps, every=1, f32=False):
+        """name -> (shape, dtype) of expert_rollout's records."""
+        return shep_rollout_shapes(int(n_steps), self.n_envs, self.n_shepherds, self.n_agents, int(every), f32)
+
+    def expert_rollout(self, n_steps, record=(), every=1, episode_length=0, reset=None, f32=False, fetch=True,
+                       device_ptrs=None, flags=None):
+        """n_steps of u = controller(); step(u) in one launch, recorded (shep_expert_rollout).
+        record: names among obs, adj (after every `every`-th step), actions, rewards, done
+        (every step's) and n_resets (B); shapes in rollout_shapes(). episode_length > 0: an
+        env whose episode step count reaches it is reset inside the launch from its own
+        stream with reset = (r_max, goal_offset). Returns a dict of host arrays and waits
+        for them; device_ptrs: {name: device address} of caller-owned buffers of those
+        shapes, written in stream order instead (only enqueues, returns None; `record` is
+        ignored); fetch=False (and no device_ptrs): nothing is recorded, only enqueues,
+        returns None. flags: the raw flag word instead of the one implied."""
+        n_steps, every = int(n_steps), int(every)
+        shapes = self.rollout_shapes(max(n_steps, 0), max(every, 1), f32)
+        rec = ShepRolloutRecords()
+
+        def put(name, addr):
+            if name not in shapes:
+                raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+            setattr(rec, name, ctypes.c_void_p(addr))
+
+        out = None
+        fl = SHEP_REC_F32 if f32 else 0
+        if device_ptrs is not None:
+            for name, addr in device_ptrs.items():
+                put(name, int(addr))
+            fl |= SHEP_REC_DEVICE
+        elif fetch:
+            out = {}
+            for name in record:
+                if name not in shapes:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+                out[name] = np.zeros(*shapes[name])
+                put(name, out[name].ctypes.data)
+        rc = None
+        if reset is not None:
+            rc = ShepResetConfig(float(reset[0]), (ctypes.c_double * 2)(float(reset[1][0]), float(reset[1][1])))
+        check(self.lib.shep_expert_rollout(self.h, n_steps, every, int(episode_length),
+                                           ctypes.byref(rc) if rc is not None else None, ctypes.byref(rec),
+                                           fl if flags is None else int(flags)))
+        return out
 
 
 class GraphUtils:

@@ -6,7 +6,10 @@ Same class name, attributes and method signatures as the reference (`__init__` :
 :275-325, `close` :327-331). The pair pass, the unicycle update, the weighted adjacency,
 the reward and the shepherd controller run in the HIP kernel of libgymflock.so
 (csrc/shepherd.hip) through the C-ABI (gym_flock._native); `reset()` draws on the host
-with NumPy, so its state is the reference's bit for bit.
+with NumPy, so its state is the reference's bit for bit. `set_reset_mode("device")` (or
+`gym_flock.make(..., reset_mode="device")`) moves the draws into one launch on
+`np_random`'s stream (csrc/shepherd_rollout.hip): the stream stays NumPy's bit for bit,
+the positions then carry the device's cos / sin.
 
 Differences a caller can observe:
   - `x` is a host mirror of the device state, fetched after every step and uploaded by
@@ -69,6 +72,9 @@ class ShepherdingEnv(Env):
         self._h = None
         self._hkey = None
         self._synced = None  # the state the device holds, as last mirrored into self.x
+        self.reset_mode = "reference"  # set_reset_mode
+        self._rng_synced = None  # np_random's state as the device last left it, and on which handle
+        self._rng_handle = None
 
         self.np_random = None
         self.seed()
@@ -117,9 +123,44 @@ class ShepherdingEnv(Env):
         self._synced = self.x.copy()
         return (obs, adj), reward, False, {}
 
+    def set_reset_mode(self, reset_mode):
+        """"reference" (default): reset() draws on the host with NumPy, the reference's
+        state bit for bit. "device": the draws run in one launch on self.np_random's stream
+        (shep_reset_device); lengths, angles and the stream afterwards are NumPy's bit for
+        bit, the positions are to the device's cos / sin instead of NumPy's."""
+        if reset_mode not in ("reference", "device"):
+            raise ValueError("reset_mode must be \"reference\" or \"device\"")
+        self.reset_mode = reset_mode
+
+    def _rng_changed(self, st):
+        s = self._rng_synced
+        return s is None or st[2] != s[2] or not np.array_equal(st[1], s[1]) or tuple(st[3:]) != tuple(s[3:])
+
+    def _reset_device(self):
+        """reset() with reset_mode="device": the stream goes up when the caller seeded or
+        drew from np_random since the last one came down; the state comes back with the
+        observation, the stream after it, so np_random stands where the reference's would."""
+        h = self._upload()
+        st = self.np_random.get_state()
+        if self._rng_handle is not h or self._rng_changed(st):
+            h.set_rng(st[:3], env=0)
+        h.reset_device(self.r_max, self.goal_offset)
+        obs, adj, _ = self._outputs(h)
+        key, pos = h.get_rng(0)
+        # a cached Gaussian (st[3:]) is the host's alone: uniform draws do not touch it
+        self._rng_synced = ("MT19937", key, pos) + tuple(st[3:])
+        self._rng_handle = h
+        self.np_random.set_state(self._rng_synced)
+        self.x = obs[:, :self.nx].copy()
+        self._synced = self.x.copy()
+        return obs, adj
+
     def reset(self):
         """:187-202: agents on a disk of radius sqrt(r_max) around goal_offset, drawn from
-        np_random on the host; headings keep their previous values, as in the reference."""
+        np_random on the host (on the device with set_reset_mode("device")); headings keep
+        their previous values, as in the reference."""
+        if self.reset_mode == "device":
+            return self._reset_device()
         self.x[:, :2] = draw_shepherding(self.n_agents, self.r_max, self.goal_offset, self.np_random)
         h = self._upload()
         h.observe()

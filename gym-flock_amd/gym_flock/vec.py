@@ -535,13 +535,38 @@ class VecShepherding:
     def reset(self, seed=0):
         """Env b draws from RandomState(seed + b) as the reference's reset() does after
         seed(seed + b) (host draws: the state is the reference's bit for bit; headings start
-        at 0). Returns the (B,N,3) state; obs() / adj() hold its observation."""
+        at 0). Returns the (B,N,3) state; obs() / adj() hold its observation. The device
+        form is reset_device(seed, headings="zero"): one launch, positions to the device's
+        cos / sin."""
         x = np.zeros((self.n_envs, self.n_agents, 3))
         for b in range(self.n_envs):
             rs = np.random.RandomState(seed + b)
             x[b, :, :2] = draw_shepherding(self.n_agents, self.r_max, self.goal_offset, rs)
         self.set_state(x)
         return x
+
+    def reset_device(self, seed=None, envs=None, headings="keep", fetch=True):
+        """reset() of the reference (:187-202) on the device, one launch for the selected
+        envs (shep_reset_device): env b draws its lengths, then its angles, from its own
+        stream, RandomState(seed + b) or, with seed None, continued where it stands
+        (np_random(b), h.set_rng). Lengths, angles and streams are NumPy's bit for bit, the
+        positions to the device's cos / sin. envs: None (all), a bool mask or an index list;
+        the other envs keep state, outputs and stream. headings: "keep" (the reference's
+        reset() does not touch them; a batch that never had a state starts from zeros) or
+        "zero". The launch also writes obs() / adj() / rewards() of the new state and zeroes
+        the selected envs' episode step counts. Returns the (B,N,3) state, or None with
+        fetch=False (nothing waits for the device then)."""
+        if headings not in ("keep", "zero"):
+            raise ValueError("headings must be 'keep' or 'zero', not %r" % (headings,))
+        self.h.reset_device(self.r_max, self.goal_offset, seed, envs, headings == "zero")
+        return self.h.get_state() if fetch else None
+
+    def np_random(self, env):
+        """A RandomState holding env `env`'s device stream."""
+        keys, pos = self.h.get_rng(env)
+        rs = np.random.RandomState()
+        rs.set_state(("MT19937", keys, pos))
+        return rs
 
     def set_state(self, x):
         """A (B,N,3) state and its observation, adjacency and reward."""
@@ -575,6 +600,33 @@ class VecShepherding:
     def expert_steps(self, n_steps, fetch=True):
         """n_steps of u = controller(); step(u) in one launch; rewards (n_steps,B)."""
         return self.h.step_expert(n_steps, fetch)
+
+    def expert_rollout(self, n_steps, record=("rewards", "done"), every=1, episode_length=None, f32=False, fetch=True,
+                       device_ptrs=None):
+        """expert_steps with records, and across episode ends, in ONE launch
+        (shep_expert_rollout): the reference driver's loop `reset(); for t in
+        range(episode_length): u = controller(); step(u)`, episode after episode on each
+        env's own stream, its output the demonstrations. record: names among obs (K,B,N,4)
+        and adj (K,B,N,N) after every `every`-th step (K = n_steps // every; `every` divides
+        n_steps), actions (n_steps,B,n_shepherds,2) (controller() of the state before the
+        step, before action_scalar), rewards (n_steps,B), done (n_steps,B) bool and n_resets
+        (B); f32: obs, adj and actions as float32. episode_length: None or 0 never resets;
+        else an env whose episode step count (h.episode_steps(); every step advances it,
+        set_state and reset_device zero it) reaches it is reset inside the launch right after
+        that step, as reset_device(envs=[b]) would reset it: done is 1 there, rewards holds
+        that step's reward, and the row recorded after it is the reset state's. So (obs()
+        before the call, actions[0]) and (obs[t], actions[t + 1]) are (observation, expert
+        action) pairs across episode ends; the terminal observation is not recorded. Needs
+        the envs' streams (reset_device(seed), h.set_rng). Returns a dict of host arrays;
+        device_ptrs: {name: device address} of caller-owned buffers
+        (h.rollout_shapes(n_steps, every, f32)), e.g. torch tensors' data_ptr(), written in
+        stream order (sync()); returns None, as with fetch=False (nothing recorded)."""
+        L = int(episode_length or 0)
+        out = self.h.expert_rollout(n_steps, record, every, L, (self.r_max, self.goal_offset) if L > 0 else None, f32,
+                                    fetch, device_ptrs)
+        if out is not None and "done" in out:
+            out["done"] = out["done"].astype(bool)
+        return out
 
     # ----------------------------------------------------------------- outputs
     def obs(self, f32=False, device_ptr=None):

@@ -909,6 +909,72 @@ int shep_get_outputs(shep_handle* h, double* dst);
 int shep_get_controls(shep_handle* h, double* dst);
 int shep_sync(shep_handle* h);
 
+/* Per-env random streams: NumPy's legacy RandomState (MT19937), a key of 624 words and a
+ * position in [0, 624] per env, as RandomState.get_state() gives them. env = -1: every
+ * env (keys (B,624), pos (B)); else one env's (624) and (1). shep_get_rng: GF_ESTATE for an
+ * env whose stream was never seeded (SHEP_RESET_SEED) or set. */
+int shep_set_rng(shep_handle* h, int env, const uint32_t* keys, const int32_t* pos);
+int shep_get_rng(shep_handle* h, int env, uint32_t* keys, int32_t* pos);
+
+typedef struct shep_reset_config {
+  double r_max;          /* self.r_max = r_max_init * sqrt(N) (:38-39); finite and > 0 */
+  double goal_offset[2]; /* self.goal_offset (:42)                                     */
+} shep_reset_config;
+#define SHEP_RESET_SEED          0x1 /* seed env b as RandomState(seed + b) first (else its
+                                        stream continues)                                 */
+#define SHEP_RESET_ZERO_HEADINGS 0x2 /* headings := 0 (else kept, as reset() :187-202
+                                        keeps x[:, 2]; a handle that never had a state
+                                        resets as from the all-zero state)                */
+/* reset() :187-202 of the selected envs (env_mask (B) bytes, NULL = all) in one launch,
+ * each from its own stream in the reference's order: length[i] = sqrt(0 + r_max * d) for
+ * all N agents, then angle[i] = pi * (0 + 2 * d), d NumPy's random_sample double of two
+ * consecutive words; x = length * cos(angle) + goal_offset[0], y = length * sin(angle) +
+ * goal_offset[1]. A reset takes 4N words. Lengths, angles and the stream afterwards are
+ * NumPy's bit for bit; cos / sin are the device's. The launch also writes the observation,
+ * adjacency and reward of the new state (as shep_observe) and zeroes the selected envs'
+ * episode step counts; the handle then has a state and an observation and no controls.
+ * Unselected envs keep state, outputs and stream; a mask that selects none does nothing.
+ * Asynchronous on the handle's stream. Before any device work: GF_EINVAL for a null handle
+ * or config, unknown flags, r_max not finite or not > 0, or (SHEP_RESET_SEED) seed +
+ * n_envs not fitting in 32 bits; GF_ESTATE for continuing the stream of a selected env
+ * that was never seeded or set. */
+int shep_reset_device(shep_handle* h, const shep_reset_config* rc, uint64_t seed, const uint8_t* env_mask, int flags);
+
+/* The envs' episode step counts (B): every stepping call advances them (shep_step 1,
+ * shep_step_expert and shep_expert_rollout n), shep_set_state and shep_reset_device (for
+ * its selected envs) zero them, and so does a reset inside shep_expert_rollout. */
+int shep_get_episode_steps(shep_handle* h, int32_t* out);
+
+typedef struct shep_rollout_records { /* every pointer may be NULL: not recorded */
+  void* obs;         /* (K,B,N,4) after every record_every-th step, K = n_steps / record_every */
+  void* adj;         /* (K,B,N,N)                                                             */
+  void* actions;     /* (n_steps,B,n_shepherds,2) controller() of the state before the step,
+                        before action_scalar                                                  */
+  double* rewards;   /* (n_steps,B)                                                           */
+  uint8_t* done;     /* (n_steps,B) 1 on an episode's last step                               */
+  int32_t* n_resets; /* (B) resets done inside this launch                                    */
+} shep_rollout_records;
+#define SHEP_REC_DEVICE 0x4 /* the records are caller-owned device memory (stream-ordered,
+                               shep_sync); else host arrays, and the call waits             */
+#define SHEP_REC_F32    0x8 /* obs, adj and actions are float32 (else float64)             */
+/* n_steps of u = controller(); step(u) in one launch, as shep_step_expert, recording on
+ * the way. episode_length = L > 0 runs the reference driver's loop `reset(); for t in
+ * range(L): u = controller(); step(u)` episode after episode: an env whose episode step
+ * count reaches L with a step has done = 1 there (rewards holds that step's reward), and
+ * its wave or workgroup then performs shep_reset_device's reset on the env's continued
+ * stream inside the launch (headings kept, count to 0). The row recorded after that step
+ * is the reset state's, so (obs before the call, actions[0]) and (obs[t], actions[t+1])
+ * are (observation, expert action) pairs across episode ends, and the terminal
+ * observation is not recorded. For every env the launch equals, bit for bit in state,
+ * outputs, last controls (the last step's, also when a reset followed it), streams and
+ * counts, the host-paced loop `shep_step(SHEP_U_EXPERT); if count >= L:
+ * shep_reset_device(mask = {b})`; launches chain. L = 0 never resets. Before any device
+ * work: GF_EINVAL for n_steps < 1, record_every < 1 or not dividing n_steps, L < 0, L > 0
+ * with a null or invalid rc, unknown flags; GF_ESTATE without a state, or with L > 0 and
+ * an env whose stream was never seeded or set. */
+int shep_expert_rollout(shep_handle* h, int n_steps, int record_every, int episode_length, const shep_reset_config* rc,
+                        const shep_rollout_records* rec, int flags);
+
 /* Diagnostics ---------------------------------------------------------------- */
 const char* fe_last_error(void);
 int fe_abi_version(void);
