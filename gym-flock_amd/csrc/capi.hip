@@ -150,7 +150,7 @@ void release(fe_handle* h) {
   if (h->fin_cnt) hipFree(h->fin_cnt);
   if (h->fin_host) hipHostFree(h->fin_host);
   for (void* p : {(void*)h->rng_key, (void*)h->rng_pos, (void*)h->reset_tries, (void*)h->reset_status,
-                  (void*)h->reset_envs})
+                  (void*)h->reset_envs, (void*)h->rng_has_gauss, (void*)h->rng_gauss, (void*)h->dt_steps})
     if (p) hipFree(p);
   if (h->reset_envs_host) hipHostFree(h->reset_envs_host);
   if (h->ev_envs) hipEventDestroy(h->ev_envs);
@@ -213,7 +213,7 @@ int packed_outputs(fe_handle* h, bool bits, gf::StepArgs& a, int* bw) {
 //     the kNN kernel that follows (rim mode) only ranks the rows it could not.
 int knn_mode(const fe_handle* h, int flags, bool dyn) {
   if (!(flags & FE_WITH_KNN) || h->cfg.n_neighbors <= 0) return 0;
-  const bool variant = h->has_variant || h->dt_per_env;
+  const bool variant = h->has_variant || h->dt_per_env || h->dt_noise;
   if (dyn && gf::step_fused_knn_ok(h->cfg.n_agents, h->R, h->cfg.n_neighbors, variant, h->prefetch != 0)) return 2;
   return 1;
 }
@@ -265,7 +265,7 @@ gf::StepArgs base_args(fe_handle* h) {
   a.u_scale = h->cfg.action_scalar;
   a.us_f = a.as_f;
   a.x_scale = 1.0;
-  if (h->has_variant || h->dt_per_env) {
+  if (h->has_variant || h->dt_per_env || h->dt_noise) {
     a.variant = 1;
     if (h->has_variant) {
       a.n_frozen = h->var.n_frozen;
@@ -278,6 +278,7 @@ gf::StepArgs base_args(fe_handle* h) {
       a.uc_f = static_cast<float>(a.u_clip);
     }
     a.dt_env = h->dt_per_env ? h->dt_env : nullptr;
+    if (h->dt_noise) a.dt_env = h->dt_steps;  // the latest draw's first row (draw_dt)
   }
   return a;
 }
@@ -532,7 +533,8 @@ int ensure_rng(fe_handle* h) {
   const size_t B = h->cfg.n_envs;
   int rc;
   if ((rc = dalloc(&h->rng_key, B * gf::kMtN)) || (rc = dalloc(&h->rng_pos, B)) || (rc = dalloc(&h->reset_tries, B)) ||
-      (rc = dalloc(&h->reset_status, B)) || (rc = dalloc(&h->reset_envs, B)))
+      (rc = dalloc(&h->reset_status, B)) || (rc = dalloc(&h->reset_envs, B)) || (rc = dalloc(&h->rng_has_gauss, B)) ||
+      (rc = dalloc(&h->rng_gauss, B)))
     return rc;
   GF_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->reset_envs_host), B * sizeof(int32_t), hipHostMallocDefault));
   GF_HIP(hipEventCreateWithFlags(&h->ev_envs, hipEventDisableTiming));
@@ -540,7 +542,47 @@ int ensure_rng(fe_handle* h) {
   GF_HIP(hipMemsetAsync(h->rng_pos, 0, B * sizeof(int32_t), h->stream));
   GF_HIP(hipMemsetAsync(h->reset_tries, 0, B * sizeof(int32_t), h->stream));
   GF_HIP(hipMemsetAsync(h->reset_status, 0, B, h->stream));
+  GF_HIP(hipMemsetAsync(h->rng_has_gauss, 0, B * sizeof(int32_t), h->stream));
+  GF_HIP(hipMemsetAsync(h->rng_gauss, 0, B * sizeof(double), h->stream));
   h->rng_set.assign(B, 0);
+  return GF_OK;
+}
+
+// fe_set_dt_noise: whether every env has a stream to draw its dt from.
+int dt_noise_ready(const fe_handle* h) {
+  bool all_set = !h->rng_set.empty();
+  for (size_t b = 0; all_set && b < h->rng_set.size(); ++b) all_set = h->rng_set[b] != 0;
+  if (!all_set)
+    return fail(GF_ESTATE, "fe_set_dt_noise: an env's stream was never seeded or set (fe_reset_device with "
+                           "FE_RESET_SEED, or fe_set_rng)");
+  return GF_OK;
+}
+
+// The next n dts of every env into dt_steps, on `stream` (the caller has joined the other
+// streams into it: use_dev).
+int draw_dt(fe_handle* h, int n) {
+  const size_t B = h->cfg.n_envs, need = B * (size_t)n;
+  if (need > h->dt_steps_cap) {
+    // (hipFree waits for whatever still reads the old table)
+    if (h->dt_steps) GF_HIP(hipFree(h->dt_steps));
+    h->dt_steps = nullptr;
+    h->dt_steps_cap = 0;
+    h->dt_rows = 0;
+    if (int rc = dalloc(&h->dt_steps, need)) return rc;
+    h->dt_steps_cap = need;
+  }
+  gf::DtNoiseArgs d{};
+  d.B = h->cfg.n_envs;
+  d.n = n;
+  d.mean = h->dt_mean;
+  d.sigma = h->dt_sigma;
+  d.mt_key = h->rng_key;
+  d.mt_pos = h->rng_pos;
+  d.has_gauss = h->rng_has_gauss;
+  d.gauss = h->rng_gauss;
+  d.dt_steps = h->dt_steps;
+  if (hipError_t e = gf::launch_dt_noise(d, h->stream); e != hipSuccess) return fail_hip("flock_dt_noise_kernel", e);
+  h->dt_rows = n;
   return GF_OK;
 }
 
@@ -821,6 +863,8 @@ int fe_reset_device(fe_handle* h, const fe_reset_config* rc, uint64_t seed, cons
   a.mt_pos = h->rng_pos;
   a.tries = h->reset_tries;
   a.status = h->reset_status;
+  a.has_gauss = h->rng_has_gauss;
+  a.gauss = h->rng_gauss;
   if (hipError_t e = gf::launch_reset(a, h->stream); e != hipSuccess) return fail_hip("flock_reset_kernel", e);
   for (int k = 0; k < n_sel; ++k) h->rng_set[env_mask ? sel[k] : k] = 1;
   GF_HIP(clear_knn_history(h));
@@ -844,8 +888,41 @@ int fe_set_rng(fe_handle* h, int env, const uint32_t* keys, const int32_t* pos) 
   GF_HIP(hipMemcpyAsync(h->rng_key + first * gf::kMtN, keys, n * gf::kMtN * sizeof(uint32_t), hipMemcpyHostToDevice,
                         h->stream));
   GF_HIP(hipMemcpyAsync(h->rng_pos + first, pos, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  // RandomState.set_state with a 3-tuple: no cached Gaussian
+  GF_HIP(hipMemsetAsync(h->rng_has_gauss + first, 0, n * sizeof(int32_t), h->stream));
+  GF_HIP(hipMemsetAsync(h->rng_gauss + first, 0, n * sizeof(double), h->stream));
   GF_HIP(hipStreamSynchronize(h->stream));
   for (size_t k = 0; k < n; ++k) h->rng_set[first + k] = 1;
+  return GF_OK;
+}
+
+int fe_set_rng_gauss(fe_handle* h, int env, const int32_t* has_gauss, const double* gauss) {
+  if (!h || !has_gauss || !gauss || env < -1) return fail(GF_EINVAL, "bad argument");
+  if (env >= 0)
+    if (int rc = check_env(h, env)) return rc;
+  const size_t n = env < 0 ? h->cfg.n_envs : 1, first = env < 0 ? 0 : env;
+  for (size_t k = 0; k < n; ++k)
+    if (has_gauss[k] != 0 && has_gauss[k] != 1) return fail(GF_EINVAL, "has_gauss must be 0 or 1");
+  if (int rc = use_dev(h)) return rc;
+  if (int rc = ensure_rng(h)) return rc;
+  GF_HIP(hipMemcpyAsync(h->rng_has_gauss + first, has_gauss, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipMemcpyAsync(h->rng_gauss + first, gauss, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
+  return GF_OK;
+}
+
+int fe_get_rng_gauss(fe_handle* h, int env, int32_t* has_gauss, double* gauss) {
+  if (!h || !has_gauss || !gauss || env < -1) return fail(GF_EINVAL, "bad argument");
+  if (env >= 0)
+    if (int rc = check_env(h, env)) return rc;
+  const size_t n = env < 0 ? h->cfg.n_envs : 1, first = env < 0 ? 0 : env;
+  for (size_t k = 0; k < n; ++k)
+    if (h->rng_set.empty() || !h->rng_set[first + k])
+      return fail(GF_ESTATE, "fe_get_rng_gauss: the env's stream was never seeded or set (fe_reset_device, fe_set_rng)");
+  if (int rc = use_dev(h)) return rc;
+  GF_HIP(hipMemcpyAsync(has_gauss, h->rng_has_gauss + first, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipMemcpyAsync(gauss, h->rng_gauss + first, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 
@@ -895,6 +972,12 @@ int fe_step(fe_handle* h, const void* u, int flags) {
   if (!h) return fail(GF_EINVAL, "null handle");
   if (!h->has_state) return fail(GF_ESTATE, "state not set (call fe_set_state first)");
   if (int rc = use_dev_step(h)) return rc;
+  if (h->dt_noise) {
+    // the step's dts are drawn on `stream` first, ordered as fe_set_dt's upload is: the
+    // streams joined, and the step one launch behind the draw
+    if (int rc = dt_noise_ready(h)) return rc;
+    if (int rc = use_dev(h)) return rc;
+  }
   const bool ctrl = flags & FE_WITH_CONTROLLER;
   bool uf64 = flags & FE_U_F64;
   const void* up = nullptr;
@@ -937,6 +1020,10 @@ int fe_step(fe_handle* h, const void* u, int flags) {
     h->main_dirty = h->other_work = true;
     up = h->u;
     h->u_resident_f64 = -1;  // the buffer now holds this call's actions
+  }
+  if (h->dt_noise) {
+    if (int rc = draw_dt(h, 1)) return rc;
+    h->other_work = true;  // (the FE_U_DEVICE path leaves it alone)
   }
   if (int rc = next_reward_slot(h)) return rc;
   gf::StepArgs a = base_args(h);
@@ -985,7 +1072,11 @@ int fe_step_expert(fe_handle* h, int n_steps, const fe_rollout* rec) {
   if (!h->has_ctrl) return fail(GF_ESTATE, "FE_U_EXPERT needs a previous controller output");
   if (h->met.comm)
     return fail(GF_ESTATE, "fe_step_expert: the handle has a communicator (its metrics ring holds 64 steps); step it with fe_step");
+  if (h->dt_noise)
+    if (int rc = dt_noise_ready(h)) return rc;
   if (int rc = use_dev(h)) return rc;  // after both halves of the latest split step
+  if (h->dt_noise)
+    if (int rc = draw_dt(h, n_steps)) return rc;
   if (int rc = next_reward_slot(h)) return rc;
 
   gf::RolloutArgs a{};
@@ -1000,6 +1091,7 @@ int fe_step_expert(fe_handle* h, int n_steps, const fe_rollout* rec) {
   if (int rc = packed_outputs(h, true, a.s, &bw)) return rc;
   a.n_steps = n_steps;
   a.record_every = every;
+  a.dt_steps = h->dt_noise ? h->dt_steps : nullptr;
 
   // records: the caller's device memory, or the staging buffer for host destinations
   const size_t K = (size_t)(n_steps / every), KBN = K * h->BN, Wn = ((size_t)N + 63) / 64;
@@ -1070,6 +1162,9 @@ static int step_host_impl(fe_handle* h, const void* u, float* state_values, floa
   if (!h) return fail(GF_EINVAL, "null handle");
   if (!h->has_state) return fail(GF_ESTATE, "state not set (call fe_set_state first)");
   if (flags & ~(FE_U_F64 | FE_WITH_CONTROLLER)) return fail(GF_EINVAL, "flags: FE_U_F64 and FE_WITH_CONTROLLER only");
+  if (h->dt_noise)
+    return fail(GF_ESTATE, "fe_step_host: the handle draws its dt on the device (fe_set_dt_noise); the drop-in env draws "
+                           "on the host and passes it with fe_set_dt");
   const bool knn = knn_idx || knn_obs;
   if (knn && h->cfg.n_neighbors <= 0) return fail(GF_EINVAL, "handle created with n_neighbors = 0");
   if (controls) flags |= FE_WITH_CONTROLLER;
@@ -1250,6 +1345,8 @@ int fe_set_variant(fe_handle* h, const fe_variant* v) {
 
 int fe_set_dt(fe_handle* h, const double* dt) {
   if (!h) return fail(GF_EINVAL, "null handle");
+  h->dt_noise = false;
+  h->dt_rows = 0;
   if (!dt) {
     h->dt_per_env = false;
     return GF_OK;
@@ -1260,6 +1357,118 @@ int fe_set_dt(fe_handle* h, const double* dt) {
   GF_HIP(hipMemcpyAsync(h->dt_env, dt, (size_t)h->cfg.n_envs * sizeof(double), hipMemcpyHostToDevice, h->stream));
   GF_HIP(hipStreamSynchronize(h->stream));
   h->dt_per_env = true;
+  return GF_OK;
+}
+
+int fe_set_dt_noise(fe_handle* h, const fe_dt_noise* nz) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!nz) {
+    h->dt_noise = false;
+    h->dt_rows = 0;
+    return GF_OK;
+  }
+  if (!std::isfinite(nz->mean) || !std::isfinite(nz->sigma) || nz->sigma < 0)
+    return fail(GF_EINVAL, "fe_set_dt_noise: mean and sigma must be finite, sigma >= 0");
+  h->dt_mean = nz->mean;
+  h->dt_sigma = nz->sigma;
+  h->dt_noise = true;
+  h->dt_per_env = false;
+  h->dt_rows = 0;
+  return GF_OK;
+}
+
+int fe_get_dt_steps(fe_handle* h, double* dst, int flags) {
+  if (!h || !dst) return fail(GF_EINVAL, "null argument");
+  if (flags & ~FE_ROLLOUT_DEVICE) return fail(GF_EINVAL, "fe_get_dt_steps: unknown flag");
+  if (!h->dt_noise || h->dt_rows < 1)
+    return fail(GF_ESTATE, "fe_get_dt_steps: no step or rollout has drawn its dt yet (fe_set_dt_noise, then a launch)");
+  if (int rc = use_dev(h)) return rc;
+  const size_t bytes = (size_t)h->dt_rows * h->cfg.n_envs * sizeof(double);
+  if (flags & FE_ROLLOUT_DEVICE) {
+    GF_HIP(hipMemcpyAsync(dst, h->dt_steps, bytes, hipMemcpyDeviceToDevice, h->stream));
+    return GF_OK;
+  }
+  return d2h(h, dst, h->dt_steps, bytes);
+}
+
+int fe_reset_variant(fe_handle* h, int kind, const fe_reset_config* rc, int n_special, uint64_t seed,
+                     const uint8_t* env_mask, int flags, int32_t* tries, uint8_t* status) {
+  if (!h || !rc) return fail(GF_EINVAL, "null argument");
+  const int N = h->cfg.n_agents, B = h->cfg.n_envs;
+  const bool seeded = flags & FE_RESET_SEED;
+  if (kind == FE_VRESET_LEADER) {
+    if (flags & ~(FE_RESET_SEED | FE_RESET_NO_REJECT)) return fail(GF_EINVAL, "fe_reset_variant: unknown flag");
+    if (n_special < 0 || n_special > N) return fail(GF_EINVAL, "fe_reset_variant: the leaders are agents [0, n_special), n_special <= n_agents");
+  } else if (kind == FE_VRESET_TWOFLOCKS) {
+    if (flags & ~FE_RESET_SEED) return fail(GF_EINVAL, "fe_reset_variant: FE_RESET_SEED only (nothing is rejected)");
+    const int side = N / 10;
+    if (side < 1 || side * (N / side) != N)
+      return fail(GF_EINVAL, "fe_reset_variant: the two flocks stand on grid(N, int(N / 10)): N >= 10 and side * int(N / side) == N");
+    if (!std::isfinite(rc->v_bias)) return fail(GF_EINVAL, "fe_reset_variant: v_bias must be finite");
+  } else if (kind == FE_VRESET_OBSTACLE) {
+    if (flags & ~FE_RESET_SEED) return fail(GF_EINVAL, "fe_reset_variant: FE_RESET_SEED only (nothing is rejected)");
+    if (N < 5 || 5 * (N / 5) != N || n_special != 4)
+      return fail(GF_EINVAL, "fe_reset_variant: the obstacle course stands on grid(N, 5) with 4 obstacles: N a multiple of 5, n_special == 4");
+  } else {
+    return fail(GF_EINVAL, "fe_reset_variant: kind is one of FE_VRESET_LEADER, FE_VRESET_TWOFLOCKS, FE_VRESET_OBSTACLE");
+  }
+  if (seeded && seed + (uint64_t)B > 0x100000000ull) return fail(GF_EINVAL, "seed + n_envs must fit in 32 bits");
+  std::vector<int32_t> sel;
+  if (env_mask)
+    for (int b = 0; b < B; ++b)
+      if (env_mask[b]) sel.push_back(b);
+  const int n_sel = env_mask ? static_cast<int>(sel.size()) : B;
+  const bool listed = env_mask && n_sel < B;
+  // nothing selected: fe_reset_device's answer (the envs' last outputs)
+  if (n_sel == 0) return fe_reset_device(h, rc, seed, env_mask, flags & FE_RESET_SEED, tries, status);
+
+  gf::VResetArgs a{};
+  if (kind == FE_VRESET_LEADER) {
+    // the relative reset of the selected envs (enqueued; it uploads the env list, which the
+    // launch below reads too), then the leaders' draw from the same streams
+    if (int r = fe_reset_device(h, rc, seed, env_mask, flags, nullptr, nullptr)) return r;
+  } else {
+    if (kind == FE_VRESET_TWOFLOCKS && !seeded) {
+      bool all_set = !h->rng_set.empty();
+      for (int k = 0; all_set && k < n_sel; ++k) all_set = h->rng_set[env_mask ? sel[k] : k] != 0;
+      if (!all_set)
+        return fail(GF_ESTATE, "fe_reset_variant: a selected env's stream was never seeded or set (FE_RESET_SEED or fe_set_rng)");
+    }
+    if (int r = use_dev(h)) return r;
+    if (int r = ensure_rng(h)) return r;
+    if (listed) {
+      GF_HIP(hipEventSynchronize(h->ev_envs));  // the previous list's upload has read the host copy
+      std::copy(sel.begin(), sel.end(), h->reset_envs_host);
+      GF_HIP(hipMemcpyAsync(h->reset_envs, h->reset_envs_host, sel.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                            h->stream));
+      GF_HIP(hipEventRecord(h->ev_envs, h->stream));
+    }
+    a.seeded = seeded ? 1 : 0;
+    a.seed0 = static_cast<uint32_t>(seed);
+  }
+  a.kind = kind;
+  a.n_sel = n_sel;
+  a.envs = listed ? h->reset_envs : nullptr;
+  a.N = N;
+  a.n_special = n_special;
+  a.v_max = rc->v_max;
+  a.v_bias = rc->v_bias;
+  a.x = h->x[h->cur];
+  a.mt_key = h->rng_key;
+  a.mt_pos = h->rng_pos;
+  a.has_gauss = h->rng_has_gauss;
+  a.gauss = h->rng_gauss;
+  a.tries = h->reset_tries;
+  a.status = h->reset_status;
+  if (hipError_t e = gf::launch_vreset(a, h->stream); e != hipSuccess) return fail_hip("flock_vreset_kernel", e);
+  if (seeded)
+    for (int k = 0; k < n_sel; ++k) h->rng_set[env_mask ? sel[k] : k] = 1;
+  GF_HIP(clear_knn_history(h));
+  h->has_state = true;
+  h->has_ctrl = h->has_obs = h->has_knn = false;
+  if (tries) GF_HIP(hipMemcpyAsync(tries, h->reset_tries, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (status) GF_HIP(hipMemcpyAsync(status, h->reset_status, (size_t)B, hipMemcpyDeviceToHost, h->stream));
+  if (tries || status) GF_HIP(hipStreamSynchronize(h->stream));
   return GF_OK;
 }
 

@@ -193,6 +193,16 @@ struct fe_handle {
   int32_t* reset_envs_host = nullptr;         // (B) page-locked: the list's upload reads it
   hipEvent_t ev_envs = nullptr;               // that upload (before the list is rewritten)
   std::vector<uint8_t> rng_set;               // (B) the env's stream was seeded or set
+  // the streams' cached Gaussian, RandomState.get_state()[3:5] (allocated with the streams)
+  int32_t* rng_has_gauss = nullptr;           // (B)
+  double* rng_gauss = nullptr;                // (B)
+  // fe_set_dt_noise: every step's dt drawn on the device (flock_dt_noise.hip) into dt_steps,
+  // which a step reads as its dt_env and a rollout as its per-step table
+  bool dt_noise = false;
+  double dt_mean = 0.0, dt_sigma = 0.0;
+  double* dt_steps = nullptr;                 // (dt_rows,B), grows on demand
+  size_t dt_steps_cap = 0;                    // doubles allocated
+  int dt_rows = 0;                            // rows the latest draw wrote (0: none yet)
 };
 
 // capi.hip: each env's get_stats means into stats_sum. Internal like the calls below, but

@@ -174,9 +174,46 @@ struct ResetArgs {
   int32_t* mt_pos;        // (B) in [0, 624]
   int32_t* tries;         // (B) out: candidates drawn
   uint8_t* status;        // (B) out: FE_RESET_EXHAUSTED
+  int32_t* has_gauss;     // (B) the streams' cached Gaussian (flock_dt_noise.hip): cleared
+  double* gauss;          // (B) for the envs a seeded reset selects
 };
 size_t reset_lds_bytes(int N, bool reject);
 hipError_t launch_reset(const ResetArgs& a, hipStream_t s);
+
+// flock_dt_noise.hip: n consecutive np.random.normal(mean, sigma) per env from the env's
+// stream (legacy_gauss with its cache), dt_steps[t * B + b] the t-th of env b.
+struct DtNoiseArgs {
+  int B, n;
+  double mean, sigma;
+  uint32_t* mt_key;       // (B,624)
+  int32_t* mt_pos;        // (B) in [0, 624]
+  int32_t* has_gauss;     // (B) RandomState.get_state()[3]
+  double* gauss;          // (B) RandomState.get_state()[4]
+  double* dt_steps;       // (n,B) out
+};
+hipError_t launch_dt_noise(const DtNoiseArgs& a, hipStream_t s);
+
+// flock_dt_noise.hip: the variants' resets (FE_VRESET_*), one wave per selected env. Leader
+// runs after launch_reset on the same envs and only overrides the leaders' velocities.
+constexpr int kVResetLeader = 1, kVResetTwoFlocks = 2, kVResetObstacle = 3;
+struct VResetArgs {
+  int kind;
+  int n_sel;
+  const int32_t* envs;    // (n_sel) or nullptr: envs 0..n_sel-1
+  int N;
+  int n_special;          // leaders / obstacles: agents [0, n_special)
+  int seeded;             // stream b := RandomState(seed0 + b) first (never with Leader: its
+  uint32_t seed0;         // rejection reset has seeded the stream already)
+  double v_max, v_bias;
+  double* x;              // (B,N,4)
+  uint32_t* mt_key;
+  int32_t* mt_pos;
+  int32_t* has_gauss;
+  double* gauss;
+  int32_t* tries;         // (B) out: 1 (TwoFlocks, Obstacle)
+  uint8_t* status;        // (B) out: 0 (TwoFlocks, Obstacle)
+};
+hipError_t launch_vreset(const VResetArgs& a, hipStream_t s);
 
 // The closed-loop expert rollout (flock_rollout.hip): n_steps of u = controller();
 // step(u) in one launch, one workgroup (of up to 1024 threads) per env that keeps the env's
@@ -197,6 +234,9 @@ struct RolloutArgs {
   int32_t* rec_deg;       // (K,B,N)
   double* rec_ctrl;       // (K,B,N,2)
   double* rec_rewards;    // (n_steps,B): every step's
+  // (n_steps,B) or nullptr: step t of env b integrates with dt_steps[t * B + b] instead of
+  // the launch's dt (variant launches only: fe_set_dt_noise)
+  const double* dt_steps;
 };
 int rollout_chunk_bits(int N);  // columns per pass-2 thread: 16, 32, 64 for N <= 64, 128, 256
 hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s);

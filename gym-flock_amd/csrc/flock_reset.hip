@@ -175,6 +175,10 @@ __global__ __launch_bounds__(kResetThreads) void flock_reset_kernel(ResetArgs a)
     a.mt_pos[b] = pos;
     a.tries[b] = tries;
     a.status[b] = ok ? 0 : kResetExhausted;
+    if (a.seeded) {  // a fresh RandomState has no cached Gaussian (flock_dt_noise.hip)
+      a.has_gauss[b] = 0;
+      a.gauss[b] = 0.0;
+    }
   }
 }
 

@@ -8,8 +8,9 @@
 // step t); each agent's state and its latest control also stay in the registers of the
 // agent's owner thread, which applies the dynamics (flock_dynamics.h, the step kernels'
 // own arithmetic) without a memory round trip. Nothing is read from global memory after
-// the first step, and nothing is written but the records and, by the last step, the
-// handle's buffers.
+// the first step (with a per-step dt table, RolloutArgs.dt_steps: one 8-byte value per
+// step, loaded a step ahead), and nothing is written but the records and, by the last
+// step, the handle's buffers.
 //
 // Thread q of row i owns the columns [q * CB, (q + 1) * CB), CB = 16, 32 or 64 for
 // N <= 64, 128, 256: a quarter of the row's adjacency bits in fe_get_network_packed's
@@ -97,7 +98,9 @@ __global__ __launch_bounds__(kRolloutThreads) void flock_rollout_kernel(RolloutA
   const double tmax = a.cr > a.cr2 ? a.cr : a.cr2;
   double dt = a.dt;
   if constexpr (VAR) {
-    if (a.dt_env) dt = a.dt_env[b];
+    // the per-step table's first row, or the launch's per-env dt
+    const double* dt0 = p.dt_steps ? p.dt_steps : a.dt_env;
+    if (dt0) dt = dt0[b];
   }
   if (tid < 2 * kRolloutWaves) {  // the slots of waves past the block's stay 0
     red1[tid >> 4][tid & 15] = double2{0.0, 0.0};
@@ -126,6 +129,14 @@ __global__ __launch_bounds__(kRolloutThreads) void flock_rollout_kernel(RolloutA
 
   for (int t = 0; t < p.n_steps; ++t) {
     St* cur = st[t & 1];
+    // the next step's dt (fe_set_dt_noise), loaded a step ahead: the one global read of a step
+    double dt_next = dt;
+    if constexpr (VAR) {
+      if (p.dt_steps && t + 1 < p.n_steps) dt_next = p.dt_steps[(size_t)(t + 1) * B + b];
+      // held in vector registers across the step: the scalar file is full (the value is
+      // the same in every lane)
+      asm volatile("" : "+v"(dt_next));
+    }
     // dynamics: the owner's registers hold the agent's state and its control
     if (owner) {
       const double2 pp{me.px, me.py}, vv{me.vx, me.vy};
@@ -287,6 +298,7 @@ __global__ __launch_bounds__(kRolloutThreads) void flock_rollout_kernel(RolloutA
         if (cd) reinterpret_cast<double2*>(cd)[d] = u;
       }
     }
+    if constexpr (VAR) dt = dt_next;
   }
   __syncthreads();  // the last step's squared deviations
   if (wid == 0) emit_reward(p.n_steps - 1);

@@ -34,6 +34,8 @@ FE_RESET_SEED = 0x1  # fe_reset_device flags
 FE_RESET_NO_REJECT = 0x2
 FE_RESET_EXHAUSTED = 0x1  # fe_reset_device status bit
 FE_ROLLOUT_DEVICE = 0x1  # fe_rollout flag: the record pointers are device memory
+FE_VRESET_LEADER, FE_VRESET_TWOFLOCKS, FE_VRESET_OBSTACLE = 1, 2, 3  # fe_reset_variant kinds
+VRESET_KINDS = {"leader": FE_VRESET_LEADER, "twoflocks": FE_VRESET_TWOFLOCKS, "obstacle": FE_VRESET_OBSTACLE}
 FE_ROLLOUT_MAX_AGENTS = 256
 
 
@@ -57,6 +59,10 @@ class FeVariant(ctypes.Structure):
     _fields_ = [("n_frozen", ctypes.c_int32), ("n_vel_zero", ctypes.c_int32),
                 ("u_scale", ctypes.c_double), ("u_clip", ctypes.c_double),
                 ("x_scale", ctypes.c_double), ("ctrl_clip", ctypes.c_double)]
+
+
+class FeDtNoise(ctypes.Structure):
+    _fields_ = [("mean", ctypes.c_double), ("sigma", ctypes.c_double)]
 
 
 class FeRollout(ctypes.Structure):
@@ -255,6 +261,11 @@ SIGNATURES = {
     "fe_reset_device": [_P, ctypes.POINTER(FeResetConfig), ctypes.c_uint64, _P, _I, _P, _P],
     "fe_set_rng": [_P, _I, _P, _P],
     "fe_get_rng": [_P, _I, _P, _P],
+    "fe_set_rng_gauss": [_P, _I, _P, _P],
+    "fe_get_rng_gauss": [_P, _I, _P, _P],
+    "fe_reset_variant": [_P, _I, ctypes.POINTER(FeResetConfig), _I, ctypes.c_uint64, _P, _I, _P, _P],
+    "fe_set_dt_noise": [_P, ctypes.POINTER(FeDtNoise)],
+    "fe_get_dt_steps": [_P, _P, _I],
     "fe_get_controls": [_P, _I, _P],
     "fe_get_rewards": [_P, _P],
     "fe_get_outputs": [_P, _I, _P, _P, _P, _I],
@@ -577,6 +588,7 @@ class FlockHandle:
                             float(action_scalar), int(bool(mean_pooling)), int(bool(centralized)),
                             int(n_neighbors), int(device))
         self.n_agents, self.n_envs, self.n_neighbors = int(n_agents), int(n_envs), int(n_neighbors)
+        self._dt_noise, self._dt_rows, self._dt_rows_max = False, 0, 1  # set_dt_noise / dt_steps
         h = ctypes.c_void_p()
         check(self.lib.fe_create(ctypes.byref(self.cfg), ctypes.byref(h)))
         self.h = h
@@ -629,12 +641,49 @@ class FlockHandle:
         check(self.lib.fe_set_variant(self.h, None))
 
     def set_dt(self, dt):
-        """Per-env dt (B,) for the following steps; None reverts to the config dt."""
+        """Per-env dt (B,) for the following steps; None reverts to the config dt. Either
+        way set_dt_noise's mode is switched off."""
+        self._dt_noise, self._dt_rows = False, 0
         if dt is None:
             check(self.lib.fe_set_dt(self.h, None))
             return
         d = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (self.n_envs,)))
         check(self.lib.fe_set_dt(self.h, ptr(d)))
+
+    def set_dt_noise(self, mean, sigma=None):
+        """Every later step draws its dt ~ N(mean, sigma) per env on the device, from the
+        env's own stream as np.random.normal would (fe_set_dt_noise; flocking_stoch.py:20);
+        set_dt_noise(None) switches it off, as set_dt() does."""
+        self._dt_rows = 0
+        if mean is None:
+            check(self.lib.fe_set_dt_noise(self.h, None))
+            self._dt_noise = False
+            return
+        nz = FeDtNoise(float(mean), float(sigma))
+        check(self.lib.fe_set_dt_noise(self.h, ctypes.byref(nz)))
+        self._dt_noise = True
+
+    def dt_steps(self, device_ptr=None):
+        """The dts the latest launch drew (fe_get_dt_steps): (n_steps, B) after step_expert,
+        (1, B) after step; GF_ESTATE before the first. device_ptr: a device address to copy
+        them to in stream order instead (returns None)."""
+        if device_ptr is not None:
+            check(self.lib.fe_get_dt_steps(self.h, ctypes.c_void_p(int(device_ptr)), FE_ROLLOUT_DEVICE))
+            return None
+        # room for the largest draw any launch of this handle asked for, failed ones included
+        out = np.empty((self._dt_rows_max, self.n_envs))
+        check(self.lib.fe_get_dt_steps(self.h, ptr(out), 0))
+        return out[:self._dt_rows].copy()
+
+    def _dt_launch(self, n):
+        """Book-keeping of a launch of n steps for dt_steps(); returns what to call on success."""
+        if not self._dt_noise:
+            return lambda: None
+        self._dt_rows_max = max(self._dt_rows_max, int(n))
+
+        def done():
+            self._dt_rows = int(n)
+        return done
 
     # -- state
     def reset_synthetic(self, seed=0, v_max=5.0):
@@ -642,14 +691,17 @@ class FlockHandle:
         check(self.lib.fe_reset_synthetic(self.h, int(seed), float(v_max)))
 
     def reset_device(self, seed=None, envs=None, reject=True, max_tries=4096, r_max=None, v_max=5.0,
-                     v_bias=None, min_dist=0.1, min_degree=2, fetch=True):
+                     v_bias=None, min_dist=0.1, min_degree=2, fetch=True, kind="relative", n_special=None):
         """reset() (flocking_relative.py:156-192) of the selected envs in one launch
         (fe_reset_device): each env's rejection sampler on its own MT19937 stream, seeded
         RandomState(seed + b) or, with seed None, continued. envs: None (all), a bool mask
         (B) or a list of env indices. reject=False keeps the first draw (the synthetic
         init). r_max defaults to sqrt(N) (params_from_cfg), v_bias to v_max. Returns
         (tries (B) int32, status (B) uint8) of every env, the unselected ones' from their
-        last reset; fetch=False only enqueues and returns None."""
+        last reset; fetch=False only enqueues and returns None.
+        kind: "relative", or a variant's reset (fe_reset_variant): "leader" (the above, then
+        one more draw into the velocities of the first n_special = 2 agents), "twoflocks"
+        (two bias draws, the grid; nothing rejected), "obstacle" (no draws; n_special = 4)."""
         n = self.n_envs
         mask = None
         if envs is not None:
@@ -666,8 +718,18 @@ class FlockHandle:
         flags = (0 if seed is None else FE_RESET_SEED) | (0 if reject else FE_RESET_NO_REJECT)
         tries = np.empty(n, np.int32) if fetch else None
         status = np.empty(n, np.uint8) if fetch else None
-        check(self.lib.fe_reset_device(self.h, ctypes.byref(rc), int(seed or 0), ptr(mask), flags,
-                                       ptr(tries), ptr(status)))
+        if kind == "relative":
+            check(self.lib.fe_reset_device(self.h, ctypes.byref(rc), int(seed or 0), ptr(mask), flags,
+                                           ptr(tries), ptr(status)))
+        else:
+            if kind not in VRESET_KINDS:
+                raise ValueError("kind: \"relative\", \"leader\", \"twoflocks\" or \"obstacle\", not %r" % (kind,))
+            if kind != "leader":
+                flags &= ~FE_RESET_NO_REJECT  # (nothing to reject)
+            if n_special is None:
+                n_special = {"leader": 2, "twoflocks": 0, "obstacle": 4}[kind]
+            check(self.lib.fe_reset_variant(self.h, VRESET_KINDS[kind], ctypes.byref(rc), int(n_special),
+                                            int(seed or 0), ptr(mask), flags, ptr(tries), ptr(status)))
         return (tries, status) if fetch else None
 
     def set_rng(self, states, env=None):
@@ -679,11 +741,27 @@ class FlockHandle:
         assert len(states) == (self.n_envs if env is None else 1)
         keys = np.empty((len(states), 624), np.uint32)
         pos = np.empty(len(states), np.int32)
+        has = np.zeros(len(states), np.int32)
+        gauss = np.zeros(len(states), np.float64)
         for b, st in enumerate(states):
             st = st.get_state() if hasattr(st, "get_state") else st
             assert st[0] == "MT19937" and len(st[1]) == 624, "a legacy RandomState (MT19937) state"
             keys[b], pos[b] = st[1], st[2]
-        check(self.lib.fe_set_rng(self.h, -1 if env is None else int(env), ptr(keys), ptr(pos)))
+            if len(st) >= 5:  # the cached Gaussian (3-tuples: none, as RandomState.set_state)
+                has[b], gauss[b] = st[3], st[4]
+        e = -1 if env is None else int(env)
+        check(self.lib.fe_set_rng(self.h, e, ptr(keys), ptr(pos)))
+        if has.any():  # (fe_set_rng has cleared the cache)
+            check(self.lib.fe_set_rng_gauss(self.h, e, ptr(has), ptr(gauss)))
+
+    def get_rng_state(self, env):
+        """Env `env`'s stream as RandomState.get_state() gives it, the cached Gaussian
+        included: ("MT19937", keys, pos, has_gauss, gauss) (fe_get_rng, fe_get_rng_gauss)."""
+        keys, pos = self.get_rng(env)
+        has = np.empty(1, np.int32)
+        gauss = np.empty(1, np.float64)
+        check(self.lib.fe_get_rng_gauss(self.h, int(env), ptr(has), ptr(gauss)))
+        return ("MT19937", keys, pos, int(has[0]), float(gauss[0]))
 
     def get_rng(self, env=None):
         """(keys (B,624) uint32, pos (B) int32) of every env's stream, or (keys (624), pos)
@@ -728,6 +806,7 @@ class FlockHandle:
         """u: host ndarray (B,N,2) (float32 arithmetic for float32/float16 actions, else
         float64, as NumPy promotes u * 10.0), or a device pointer (int) with FE_U_DEVICE,
         or None with FE_U_EXPERT / FE_U_RESIDENT."""
+        done = self._dt_launch(1)
         if flags & (FE_U_EXPERT | FE_U_RESIDENT):
             check(self.lib.fe_step(self.h, None, int(flags)))
         elif flags & FE_U_DEVICE:
@@ -743,9 +822,11 @@ class FlockHandle:
             u = np.ascontiguousarray(u)
             assert u.shape == (self.n_envs, self.n_agents, 2), u.shape
             check(self.lib.fe_step(self.h, ptr(u), int(flags)))
+        done()
 
     def rollout_shapes(self, n_steps, every=1):
-        """name -> (shape, dtype) of fe_step_expert's records (fe_rollout)."""
+        """name -> (shape, dtype) of fe_step_expert's records (fe_rollout). (With set_dt_noise
+        step_expert also takes "dt": (n_steps, B) float64, fe_get_dt_steps.)"""
         k, b, n = n_steps // every, self.n_envs, self.n_agents
         return {"x": ((k, b, n, 4), np.float64), "state_values": ((k, b, n, 6), np.float32),
                 "adj_bits": ((k, b, n, (n + 63) // 64), np.uint64), "degree": ((k, b, n), np.int32),
@@ -765,20 +846,38 @@ class FlockHandle:
         rec = FeRollout()
         rec.record_every = every
         out = None
+        # "dt" (set_dt_noise only): every step's dt, (n_steps, B), read from the handle's
+        # table after the launch (fe_get_dt_steps), not a field of fe_rollout
+        dt_addr, want_dt = None, False
+        names = sorted(shapes) + ["dt"]
         if device_ptrs is not None:
             for name, addr in device_ptrs.items():
-                if name not in shapes:
-                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
-                setattr(rec, name, ctypes.c_void_p(int(addr)))
+                if name not in names:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(names)))
+                if name == "dt":
+                    dt_addr = int(addr)
+                else:
+                    setattr(rec, name, ctypes.c_void_p(int(addr)))
             rec.flags = FE_ROLLOUT_DEVICE
         elif fetch:
             out = {}
             for name in record:
-                if name not in shapes:
-                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+                if name not in names:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(names)))
+                if name == "dt":
+                    want_dt = True
+                    continue
                 out[name] = np.empty(*shapes[name])
                 setattr(rec, name, out[name].ctypes.data_as(ctypes.c_void_p))
+        if (want_dt or dt_addr is not None) and not self._dt_noise:
+            raise GymFlockError(GF_ESTATE, "the \"dt\" record needs set_dt_noise (a fixed dt is the caller's own)")
+        done = self._dt_launch(n_steps)
         check(self.lib.fe_step_expert(self.h, n_steps, ctypes.byref(rec)))
+        done()
+        if want_dt:
+            out["dt"] = self.dt_steps()
+        elif dt_addr is not None:
+            self.dt_steps(device_ptr=dt_addr)
         return out
 
     def step_host(self, u_addr, f64, sv, net, rew, ctrl):

@@ -28,11 +28,14 @@ class VecFlockingRelative:
     env_offset: global index of this shard's first env (seeds are env_offset + b),
     so a batch sharded over ranks reproduces the single-device batch.
     variant: a VARIANTS key or a dict of fe_variant fields (flocking variants).
+    dt_noise: (mean, sigma): every step's dt is drawn ~ N(mean, sigma) per env on the
+    device, from the env's own stream (FlockingStochastic-v0: (0.12, 0.018); the streams
+    come from reset_device(seed) or h.set_rng). variant="stochastic" alone keeps a fixed dt.
     """
 
     def __init__(self, n_envs, n_agents, comm_radius=0.9, dt=0.01, v_max=5.0,
                  action_scalar=10.0, mean_pooling=True, centralized=True, n_neighbors=0,
-                 device=0, env_offset=0, variant=None):
+                 device=0, env_offset=0, variant=None, dt_noise=None):
         self.n_envs, self.n_agents = int(n_envs), int(n_agents)
         self.v_max = v_max
         self.env_offset = int(env_offset)
@@ -41,6 +44,8 @@ class VecFlockingRelative:
         v = VARIANTS[variant] if isinstance(variant, str) else variant
         if v:
             self.h.set_variant(**v)
+        if dt_noise is not None:
+            self.h.set_dt_noise(*dt_noise)
 
     # ------------------------------------------------------------------- state
     def reset(self, seed=0, x=None):
@@ -51,7 +56,8 @@ class VecFlockingRelative:
         self.h.compute_helpers()
         return x
 
-    def reset_device(self, seed=None, envs=None, reject=True, max_tries=4096, r_max=None, fetch=True):
+    def reset_device(self, seed=None, envs=None, reject=True, max_tries=4096, r_max=None, fetch=True,
+                     kind="relative"):
         """reset() of the reference (flocking_relative.py:156-192) on the device, one launch
         for the selected envs: env b draws from its own stream, RandomState(seed + env_offset
         + b) or, with seed None, continued where its last reset left it, until a draw passes
@@ -61,17 +67,23 @@ class VecFlockingRelative:
         resets the envs whose episode ended between two steps. reject=False keeps the first
         draw (reset()'s synthetic init, any N). r_max: the reference's self.r_max, sqrt(N)
         by default. Ends with compute_helpers(). Returns (tries, status) per env, or None
-        with fetch=False (nothing waits for the device then)."""
+        with fetch=False (nothing waits for the device then).
+        kind: the variants' own resets from the same streams (fe_reset_variant): "leader"
+        (flocking_leader.py:37-41: the reset above, then one draw into both leaders'
+        velocities; unlike the reference's reset(), the observation computed here is of the
+        state after that override), "twoflocks" (flocking_twoflocks.py:8-28, n_agents a
+        multiple of int(n_agents / 10)) and "obstacle" (flocking_obstacle.py:59-74, no
+        draws, n_agents a multiple of 5); the last two report tries = 1."""
         s = None if seed is None else int(seed) + self.env_offset
-        out = self.h.reset_device(s, envs, reject, max_tries, r_max, self.v_max, fetch=fetch)
+        out = self.h.reset_device(s, envs, reject, max_tries, r_max, self.v_max, fetch=fetch, kind=kind)
         self.h.compute_helpers()
         return out
 
     def np_random(self, env):
-        """A RandomState at env `env`'s device stream position (after its last reset)."""
-        keys, pos = self.h.get_rng(env)
+        """A RandomState at env `env`'s device stream position (after its last reset or dt
+        draw), its cached Gaussian included."""
         rs = np.random.RandomState()
-        rs.set_state(("MT19937", keys, pos))
+        rs.set_state(self.h.get_rng_state(env))
         return rs
 
     def set_state(self, x):
@@ -125,7 +137,8 @@ class VecFlockingRelative:
         record: what to keep of every `every`-th step (`every` divides n_steps), among
         "x" (K,B,N,4), "state_values" (K,B,N,6), "adj_bits" (K,B,N,ceil(N/64)) uint64,
         "degree" (K,B,N), "controls" (K,B,N,2) (the controller of the recorded state) with
-        K = n_steps // every, and "rewards" (n_steps,B), always every step's. Returns a
+        K = n_steps // every, and "rewards" (n_steps,B), always every step's; with dt_noise
+        also "dt" (n_steps,B), the dt every step integrated with. Returns a
         dict of arrays. device_ptrs={name: device address}: those records are written to
         the caller's device buffers in stream order instead (e.g. tensor.data_ptr());
         nothing waits and None is returned, as with fetch=False (nothing recorded).

@@ -173,6 +173,42 @@ int fe_reset_device(fe_handle* h, const fe_reset_config* rc, uint64_t seed, cons
  * positions in [0, 624]. env = -1: all envs, keys (B,624) and pos (B); else one env's. */
 int fe_set_rng(fe_handle* h, int env /* -1 = all */, const uint32_t* keys /* (.,624) */, const int32_t* pos);
 int fe_get_rng(fe_handle* h, int env, uint32_t* keys, int32_t* pos);
+/* The rest of RandomState.get_state(): the Gaussian that legacy_gauss drew with the last
+ * one and has not handed out yet (has_gauss 0 or 1, and its value). Only the dt draws of
+ * fe_set_dt_noise use it. fe_set_rng and a reset with FE_RESET_SEED clear it for the envs
+ * they touch, as RandomState.set_state with a 3-tuple and a fresh RandomState(seed) do; a
+ * continued reset leaves it alone (uniform does not touch it). env = -1: all envs, (B)
+ * each; else one env's. fe_get_rng_gauss: GF_ESTATE for a stream never seeded or set. */
+int fe_set_rng_gauss(fe_handle* h, int env /* -1 = all */, const int32_t* has_gauss, const double* gauss);
+int fe_get_rng_gauss(fe_handle* h, int env, int32_t* has_gauss, double* gauss);
+
+/* The variants' resets on the device, from the same per-env streams, one wave per selected
+ * env. env_mask, seed, flags, tries and status work as in fe_reset_device; afterwards the
+ * handle is as after fe_set_state_env of the new state.
+ *  FE_VRESET_LEADER (flocking_leader.py:37-41): fe_reset_device's launch (rc, FE_RESET_SEED,
+ *    FE_RESET_NO_REJECT as there), then one more random_sample u per selected env from the
+ *    same stream: w = -v_max + (v_max - -v_max) * u becomes both velocity components of
+ *    agents [0, n_special) (0 <= n_special <= n_agents). The reference computes its reset
+ *    observation and the first controller output from the state BEFORE that override; this
+ *    call leaves the overridden state, and fe_compute_helpers / fe_controller after it see
+ *    the leaders' new velocities. The quirk stays with the drop-in FlockingLeaderEnv, which
+ *    resets on the host.
+ *  FE_VRESET_TWOFLOCKS (flocking_twoflocks.py:8-28): two uniforms in [-v_bias/2, v_bias/2)
+ *    (rc->v_bias), positions 0.8 * grid(N, side = int(N/10)) with x fastest, velocities
+ *    -position + bias. GF_EINVAL unless side >= 1 and side * int(N/side) == N. n_special
+ *    and the rest of rc are ignored. tries = 1, status = 0. GF_ESTATE without FE_RESET_SEED
+ *    for a stream never seeded or set.
+ *  FE_VRESET_OBSTACLE (flocking_obstacle.py:59-74): no draws (FE_RESET_SEED still seeds the
+ *    streams). The flock on grid(N, 5) at velocity (0, -7), the n_special == 4 obstacles on
+ *    half of grid(4, 2) moved 10 down, at rest. GF_EINVAL unless 5 * int(N/5) == N and
+ *    n_special == 4. tries = 1, status = 0.
+ * TwoFlocks and Obstacle take FE_RESET_SEED only. */
+#define FE_VRESET_LEADER 1
+#define FE_VRESET_TWOFLOCKS 2
+#define FE_VRESET_OBSTACLE 3
+int fe_reset_variant(fe_handle* h, int kind, const fe_reset_config* rc, int n_special, uint64_t seed,
+                     const uint8_t* env_mask /* (B) or NULL = all */, int flags, int32_t* tries /* (B) host or NULL */,
+                     uint8_t* status /* (B) host or NULL */);
 
 /* Hot path ------------------------------------------------------------------- */
 /* Upload (B,N,2) actions (float32, or float64 if f64) into the handle's resident
@@ -193,7 +229,7 @@ int fe_step(fe_handle* h, const void* u, int flags);
  * an env's state in LDS across all steps, so n_agents <= 256 (every size at which the
  * reference's reset() ever accepts a draw); GF_EINVAL above: loop over
  * fe_step(FE_U_EXPERT) there. Variants (fe_set_variant) and a per-env dt (fe_set_dt, the
- * same dt for all n_steps) apply as in fe_step.
+ * same dt for all n_steps; fe_set_dt_noise, a new one every step) apply as in fe_step.
  * rec (or NULL: nothing recorded): where to put step t's record for every t with
  * (t + 1) % record_every == 0, K = n_steps / record_every of them, and every step's reward.
  * Every pointer may be NULL (not recorded). */
@@ -322,6 +358,29 @@ int fe_set_variant(fe_handle* h, const fe_variant* v);
 /* Per-env dt[B] for the following steps (FlockingStochastic-v0 draws one per step,
  * flocking_stoch.py:24); NULL reverts to cfg dt. */
 int fe_set_dt(fe_handle* h, const double* dt);
+/* FlockingStochastic-v0's dt ~ N(mean, sigma) of every step (flocking_stoch.py:20) drawn on
+ * the device: NumPy's legacy np.random.normal on env b's own stream (fe_set_rng,
+ * fe_reset_device), its cached second Gaussian included (fe_set_rng_gauss). NULL: off.
+ * While the mode is on
+ *  - fe_step (any action source or flags) first draws one dt per env, fe_step_expert
+ *    n_steps per env (step t of env b integrates with the t-th), on the handle's stream
+ *    after all of its outstanding work; the step then goes out as one launch behind the draw,
+ *    as after fe_set_dt's upload. The variant code path is taken as with fe_set_dt.
+ *  - GF_ESTATE from those calls if any env's stream was never seeded or set;
+ *  - fe_step_host* return GF_ESTATE (the drop-in env draws on the host);
+ *  - sigma == 0 still consumes the stream, as NumPy does.
+ * GF_EINVAL for sigma < 0 or a non-finite value. fe_set_dt (NULL or an array) switches the
+ * mode off; switching it on replaces a per-env dt set before. The uniforms, the rejection
+ * test, the division and the square root are NumPy's bit for bit; the device's log may
+ * differ from the host's in the last places, so a dt lies within sigma * |g| * 4 * 2^-52 +
+ * 2^-53 * |dt| of NumPy's (g the standard Gaussian behind it). */
+typedef struct fe_dt_noise { double mean, sigma; } fe_dt_noise;
+int fe_set_dt_noise(fe_handle* h, const fe_dt_noise* noise /* NULL: off */);
+/* The dts of the latest launch while the mode is on: (n_steps, B) after fe_step_expert,
+ * (1, B) after fe_step. flags 0: dst is host memory, the call waits; FE_ROLLOUT_DEVICE: dst
+ * is device memory, copied in stream order. GF_ESTATE before the first such launch (and
+ * after the mode was switched off or on again). */
+int fe_get_dt_steps(fe_handle* h, double* dst, int flags);
 
 /* Multi-GPU metrics path (RCCL over xGMI) ---------------------- */
 /* The env batch is sharded contiguously over ranks (one process per GPU); the
