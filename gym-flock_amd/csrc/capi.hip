@@ -147,6 +147,8 @@ void release(fe_handle* h) {
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->roll_stage) hipFree(h->roll_stage);
+  for (void* p : {(void*)h->pol_image, (void*)h->taps, (void*)h->mix_mask})
+    if (p) hipFree(p);
   if (h->fin_cnt) hipFree(h->fin_cnt);
   if (h->fin_host) hipHostFree(h->fin_host);
   for (void* p : {(void*)h->rng_key, (void*)h->rng_pos, (void*)h->reset_tries, (void*)h->reset_status,
@@ -596,6 +598,58 @@ int ensure_ucopy(fe_handle* h) {
     GF_HIP(hipEventCreateWithFlags(&h->ev_uread[k][1], hipEventDisableTiming));
   }
   GF_HIP(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
+  return GF_OK;
+}
+
+// The tails the rollouts share (fe_step_expert, fe_step_policy). A record goes to the caller's
+// device memory or, for a host destination, through the handle's staging buffer (grow-only).
+struct RolloutPart {
+  void* dst;      // the caller's destination, or nullptr: not recorded
+  size_t bytes, off;
+};
+
+// dev[k]: where the kernel writes part k (nullptr: not recorded).
+int rollout_destinations(fe_handle* h, RolloutPart* parts, int n, bool to_host, void** dev) {
+  if (!to_host) {
+    for (int k = 0; k < n; ++k) dev[k] = parts[k].dst;
+    return GF_OK;
+  }
+  size_t total = 0;
+  for (int k = 0; k < n; ++k)
+    if (parts[k].dst) {
+      parts[k].off = total;
+      total += (parts[k].bytes + 255) & ~(size_t)255;
+    }
+  if (total > h->roll_stage_bytes) {
+    // whatever read the old buffer was waited for by the call that issued it
+    if (h->roll_stage) GF_HIP(hipFree(h->roll_stage));
+    h->roll_stage = nullptr;
+    h->roll_stage_bytes = 0;
+    if (int rc = dalloc(&h->roll_stage, total)) return rc;
+    h->roll_stage_bytes = total;
+  }
+  for (int k = 0; k < n; ++k) dev[k] = parts[k].dst ? h->roll_stage + parts[k].off : nullptr;
+  return GF_OK;
+}
+
+// After the rollout's launch: the handle's buffers are the final state's (bits buffer bw),
+// and host destinations are filled from the staging buffer before the call returns.
+int rollout_finish(fe_handle* h, int bw, const RolloutPart* parts, void* const* dev, int n, bool to_host) {
+  GF_HIP(clear_knn_history(h));
+  h->cur ^= 1;
+  h->ccur ^= 1;
+  h->bits_cur = bw;
+  h->has_ctrl = h->has_obs = h->has_packed = true;
+  h->obs_on_host = false;
+  h->has_knn = false;
+  h->net_stale = true;           // the dense network still describes the state before the rollout
+  h->net_record_valid = false;   // and the next plain step stores it in full
+  if (to_host) {
+    for (int k = 0; k < n; ++k)
+      if (parts[k].dst)
+        GF_HIP(hipMemcpyAsync(parts[k].dst, dev[k], parts[k].bytes, hipMemcpyDeviceToHost, h->stream));
+    GF_HIP(hipStreamSynchronize(h->stream));
+  }
   return GF_OK;
 }
 
@@ -1096,10 +1150,7 @@ int fe_step_expert(fe_handle* h, int n_steps, const fe_rollout* rec) {
   // records: the caller's device memory, or the staging buffer for host destinations
   const size_t K = (size_t)(n_steps / every), KBN = K * h->BN, Wn = ((size_t)N + 63) / 64;
   const bool to_host = rec && !(rec->flags & FE_ROLLOUT_DEVICE);
-  struct Part {
-    void* dst;
-    size_t bytes, off;
-  } parts[6] = {};
+  RolloutPart parts[6] = {};
   if (rec) {
     parts[0] = {rec->x, KBN * 4 * sizeof(double), 0};
     parts[1] = {rec->state_values, KBN * 6 * sizeof(float), 0};
@@ -1109,26 +1160,7 @@ int fe_step_expert(fe_handle* h, int n_steps, const fe_rollout* rec) {
     parts[5] = {rec->rewards, (size_t)n_steps * B * sizeof(double), 0};
   }
   void* dev[6] = {};
-  if (to_host) {
-    size_t total = 0;
-    for (Part& q : parts)
-      if (q.dst) {
-        q.off = total;
-        total += (q.bytes + 255) & ~(size_t)255;
-      }
-    if (total > h->roll_stage_bytes) {
-      // whatever read the old buffer was waited for by the call that issued it
-      if (h->roll_stage) GF_HIP(hipFree(h->roll_stage));
-      h->roll_stage = nullptr;
-      h->roll_stage_bytes = 0;
-      if (int rc = dalloc(&h->roll_stage, total)) return rc;
-      h->roll_stage_bytes = total;
-    }
-    for (int k = 0; k < 6; ++k)
-      if (parts[k].dst) dev[k] = h->roll_stage + parts[k].off;
-  } else {
-    for (int k = 0; k < 6; ++k) dev[k] = parts[k].dst;
-  }
+  if (int rc = rollout_destinations(h, parts, 6, to_host, dev)) return rc;
   a.rec_x = static_cast<double*>(dev[0]);
   a.rec_sv = static_cast<float*>(dev[1]);
   a.rec_bits = static_cast<uint64_t*>(dev[2]);
@@ -1137,22 +1169,215 @@ int fe_step_expert(fe_handle* h, int n_steps, const fe_rollout* rec) {
   a.rec_rewards = static_cast<double*>(dev[5]);
 
   if (hipError_t e = gf::launch_rollout(a, h->stream); e != hipSuccess) return fail_hip("flock_rollout_kernel launch", e);
-  GF_HIP(clear_knn_history(h));
-  h->cur ^= 1;
-  h->ccur ^= 1;
-  h->bits_cur = bw;
-  h->has_ctrl = h->has_obs = h->has_packed = true;
-  h->obs_on_host = false;
-  h->has_knn = false;
-  h->net_stale = true;           // the dense network still describes the state before the rollout
-  h->net_record_valid = false;   // and the next plain step stores it in full
-  if (to_host) {
-    for (int k = 0; k < 6; ++k)
-      if (parts[k].dst)
-        GF_HIP(hipMemcpyAsync(parts[k].dst, dev[k], parts[k].bytes, hipMemcpyDeviceToHost, h->stream));
-    GF_HIP(hipStreamSynchronize(h->stream));
+  return rollout_finish(h, bw, parts, dev, 6, to_host);
+}
+
+// The learner of fe_step_policy: validated, packed into the kernel's LDS layout
+// (gf::policy_pack_image) and uploaded; the taps of every env start from zero.
+int fe_set_policy(fe_handle* h, const fe_policy* pol) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!pol) {
+    if (int rc = use_dev(h)) return rc;
+    if (h->taps && h->taps_cap) GF_HIP(hipMemsetAsync(h->taps, 0, h->taps_cap * sizeof(float), h->stream));
+    h->has_policy = false;
+    return GF_OK;
+  }
+  const int K = pol->n_taps, L = pol->n_layers;
+  if (K < 1 || K > gf::kPolicyMaxTaps) return fail(GF_EINVAL, "fe_set_policy: n_taps must be 1..4");
+  if (L < 1 || L > gf::kPolicyMaxLayers) return fail(GF_EINVAL, "fe_set_policy: n_layers must be 1..3");
+  if (pol->activation != FE_ACT_RELU) return fail(GF_EINVAL, "fe_set_policy: unknown activation (FE_ACT_RELU)");
+  if (!(pol->clip >= 0.0)) return fail(GF_EINVAL, "fe_set_policy: clip must be >= 0 (0: none)");
+  if (pol->width[0] != 6 * K || pol->width[L] != 2)
+    return fail(GF_EINVAL, "fe_set_policy: width[0] must be 6 * n_taps and width[n_layers] 2");
+  for (int l = 1; l < L; ++l)
+    if (pol->width[l] < 4 || pol->width[l] > gf::kPolicyMaxWidth || pol->width[l] % 4 != 0)
+      return fail(GF_EINVAL, "fe_set_policy: hidden widths must be multiples of 4, at most 64");
+  for (int l = 0; l < L; ++l)
+    if (!pol->weight[l] || !pol->bias[l]) return fail(GF_EINVAL, "fe_set_policy: null weight or bias");
+  if (int rc = use_dev(h)) return rc;
+  gf::PolicyNet n{};
+  n.n_layers = L;
+  n.n_taps = K;
+  for (int l = 0; l <= L; ++l) n.width[l] = pol->width[l];
+  n.n_floats = gf::policy_image_floats(L, n.width, n.off_w, n.off_b);
+  n.clip = static_cast<float>(pol->clip);
+  std::vector<float> image((size_t)n.n_floats);
+  gf::policy_pack_image(L, n.width, pol->weight, pol->bias, image.data());
+  if ((size_t)n.n_floats > h->pol_image_cap) {
+    if (h->pol_image) GF_HIP(hipFree(h->pol_image));  // (waits for whatever still reads it)
+    h->pol_image = nullptr;
+    h->pol_image_cap = 0;
+    h->has_policy = false;
+    if (int rc = dalloc(&h->pol_image, (size_t)n.n_floats)) return rc;
+    h->pol_image_cap = (size_t)n.n_floats;
+  }
+  const size_t nt = h->BN * (size_t)(K - 1) * 6;
+  if (nt > h->taps_cap) {
+    if (h->taps) GF_HIP(hipFree(h->taps));
+    h->taps = nullptr;
+    h->taps_cap = 0;
+    h->has_policy = false;
+    if (int rc = dalloc(&h->taps, nt)) return rc;
+    h->taps_cap = nt;
+  }
+  GF_HIP(hipMemcpyAsync(h->pol_image, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (nt) GF_HIP(hipMemsetAsync(h->taps, 0, nt * sizeof(float), h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));  // `image` is the call's own
+  n.image = h->pol_image;
+  h->policy = n;
+  h->has_policy = true;
+  return GF_OK;
+}
+
+int fe_reset_aggregation(fe_handle* h, const uint8_t* env_mask) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  if (!h->has_policy) return fail(GF_ESTATE, "fe_reset_aggregation: no policy set (fe_set_policy)");
+  const size_t per_env = (size_t)h->cfg.n_agents * (h->policy.n_taps - 1) * 6;
+  if (!per_env) return GF_OK;
+  if (int rc = use_dev(h)) return rc;
+  const int B = h->cfg.n_envs;
+  // one memset per run of selected envs
+  for (int b = 0; b < B;) {
+    if (env_mask && !env_mask[b]) {
+      ++b;
+      continue;
+    }
+    int e = b + 1;
+    while (e < B && (!env_mask || env_mask[e])) ++e;
+    GF_HIP(hipMemsetAsync(h->taps + (size_t)b * per_env, 0, (size_t)(e - b) * per_env * sizeof(float), h->stream));
+    b = e;
   }
   return GF_OK;
+}
+
+int fe_get_aggregation(fe_handle* h, int env, float* dst) {
+  if (!h || !dst) return fail(GF_EINVAL, "null argument");
+  const int N = h->cfg.n_agents, B = h->cfg.n_envs;
+  if (env < -1 || env >= B) return fail(GF_EINVAL, "fe_get_aggregation: env out of range");
+  if (!h->has_policy) return fail(GF_ESTATE, "fe_get_aggregation: no policy set (fe_set_policy)");
+  if (!h->has_obs || h->obs_on_host) return fail(GF_ESTATE, "fe_get_aggregation: no device observation of the current state");
+  if (int rc = use_dev(h)) return rc;
+  const int K = h->policy.n_taps;
+  const size_t rows = (size_t)(env < 0 ? B : 1) * N, first = (size_t)(env < 0 ? 0 : env) * N;
+  std::vector<float> sv(rows * 6), tp(rows * (size_t)(K - 1) * 6);
+  GF_HIP(hipMemcpyAsync(sv.data(), h->sv + first * 6, sv.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (!tp.empty())
+    GF_HIP(hipMemcpyAsync(tp.data(), h->taps + first * (K - 1) * 6, tp.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  GF_HIP(hipStreamSynchronize(h->stream));
+  for (size_t r = 0; r < rows; ++r) {
+    float* d = dst + r * (size_t)K * 6;
+    for (int f = 0; f < 6; ++f) d[f] = sv[r * 6 + f];
+    for (int i = 0; i < (K - 1) * 6; ++i) d[6 + i] = tp[r * (size_t)(K - 1) * 6 + i];
+  }
+  return GF_OK;
+}
+
+int fe_step_policy(fe_handle* h, int n_steps, double beta, const fe_policy_rollout* rec) {
+  if (!h) return fail(GF_EINVAL, "null handle");
+  const int N = h->cfg.n_agents, B = h->cfg.n_envs;
+  if (n_steps < 1) return fail(GF_EINVAL, "fe_step_policy: n_steps must be >= 1");
+  if (!(beta >= 0.0 && beta <= 1.0)) return fail(GF_EINVAL, "fe_step_policy: beta must be in [0, 1]");
+  if (N > gf::kRolloutMaxN)
+    return fail(GF_EINVAL, "fe_step_policy: a rollout keeps an env's state in LDS, n_agents <= 256");
+  const int every = rec ? rec->record_every : 1;
+  if (rec) {
+    if (rec->flags & ~FE_ROLLOUT_DEVICE) return fail(GF_EINVAL, "fe_step_policy: unknown flag");
+    if (every < 1 || n_steps % every != 0) return fail(GF_EINVAL, "fe_step_policy: record_every must be >= 1 and divide n_steps");
+  }
+  if (h->has_variant || h->dt_per_env || h->dt_noise)
+    return fail(GF_EINVAL, "fe_step_policy: FlockingRelative only (no fe_set_variant, fe_set_dt or fe_set_dt_noise)");
+  if (!h->has_policy) return fail(GF_ESTATE, "fe_step_policy: no policy set (fe_set_policy)");
+  if (!h->has_state) return fail(GF_ESTATE, "state not set (call fe_set_state first)");
+  if (!h->has_ctrl || !h->has_obs || h->obs_on_host)
+    return fail(GF_ESTATE, "fe_step_policy needs a controller output and the device observation of the current state");
+  if (h->met.comm)
+    return fail(GF_ESTATE, "fe_step_policy: the handle has a communicator (its metrics ring holds 64 steps); step it with fe_step");
+  const bool draws = beta > 0.0 && beta < 1.0;
+  if (draws) {
+    bool all_set = !h->rng_set.empty();
+    for (size_t b = 0; all_set && b < h->rng_set.size(); ++b) all_set = h->rng_set[b] != 0;
+    if (!all_set)
+      return fail(GF_ESTATE, "fe_step_policy: 0 < beta < 1 draws from every env's stream, and one was never seeded or "
+                             "set (fe_reset_device with FE_RESET_SEED, or fe_set_rng)");
+  }
+  const gf::PolicyNet& net = h->policy;
+  // the same expression as the launch's
+  if (gf::policy_rollout_lds_bytes(N, net.n_taps, net.n_floats) > gf::kPolicyLdsMax)
+    return fail(GF_EINVAL, "fe_step_policy: the network and the taps do not fit the workgroup's LDS");
+  if (int rc = use_dev(h)) return rc;
+  if (draws) {
+    const size_t need = (size_t)n_steps * B;
+    if (need > h->mix_mask_cap) {
+      if (h->mix_mask) GF_HIP(hipFree(h->mix_mask));
+      h->mix_mask = nullptr;
+      h->mix_mask_cap = 0;
+      if (int rc = dalloc(&h->mix_mask, need)) return rc;
+      h->mix_mask_cap = need;
+    }
+  }
+  if (int rc = next_reward_slot(h)) return rc;
+
+  gf::PolicyRolloutArgs a{};
+  a.r.s = base_args(h);
+  a.r.s.x_in = h->x[h->cur];
+  a.r.s.x_out = h->x[h->cur ^ 1];
+  a.r.s.u = h->ctrl[h->ccur];
+  a.r.s.ctrl_out = h->ctrl[h->ccur ^ 1];
+  a.r.s.state_values = h->sv;
+  a.r.s.reward = cur_reward(h);
+  int bw = -1;
+  if (int rc = packed_outputs(h, true, a.r.s, &bw)) return rc;
+  a.r.n_steps = n_steps;
+  a.r.record_every = every;
+  a.net = net;
+  a.taps = net.n_taps > 1 ? h->taps : nullptr;
+  a.mask = draws ? h->mix_mask : nullptr;
+  a.mask_const = beta >= 1.0 ? 1 : 0;
+
+  const size_t K = (size_t)(n_steps / every), KBN = K * h->BN, Wn = ((size_t)N + 63) / 64;
+  const bool to_host = rec && !(rec->flags & FE_ROLLOUT_DEVICE);
+  constexpr int kParts = 10;
+  RolloutPart parts[kParts] = {};
+  if (rec) {
+    parts[0] = {rec->x, KBN * 4 * sizeof(double), 0};
+    parts[1] = {rec->state_values, KBN * 6 * sizeof(float), 0};
+    parts[2] = {rec->adj_bits, KBN * Wn * sizeof(uint64_t), 0};
+    parts[3] = {rec->degree, KBN * sizeof(int32_t), 0};
+    parts[4] = {rec->controls, KBN * 2 * sizeof(double), 0};
+    parts[5] = {rec->rewards, (size_t)n_steps * B * sizeof(double), 0};
+    parts[6] = {rec->agg, KBN * (size_t)net.n_taps * 6 * sizeof(float), 0};
+    parts[7] = {rec->policy, KBN * 2 * sizeof(float), 0};
+    parts[8] = {rec->applied, (size_t)n_steps * h->BN * 2 * sizeof(double), 0};
+    parts[9] = {rec->used_expert, (size_t)n_steps * B, 0};
+  }
+  void* dev[kParts] = {};
+  if (int rc = rollout_destinations(h, parts, kParts, to_host, dev)) return rc;
+  a.r.rec_x = static_cast<double*>(dev[0]);
+  a.r.rec_sv = static_cast<float*>(dev[1]);
+  a.r.rec_bits = static_cast<uint64_t*>(dev[2]);
+  a.r.rec_deg = static_cast<int32_t*>(dev[3]);
+  a.r.rec_ctrl = static_cast<double*>(dev[4]);
+  a.r.rec_rewards = static_cast<double*>(dev[5]);
+  a.rec_agg = static_cast<float*>(dev[6]);
+  a.rec_policy = static_cast<float*>(dev[7]);
+  a.rec_applied = static_cast<double*>(dev[8]);
+  a.rec_used = static_cast<uint8_t*>(dev[9]);
+
+  // the draws last: nothing between them and the rollout's launch can fail and leave the
+  // streams advanced without a step
+  if (draws) {
+    gf::MixMaskArgs m{};
+    m.B = B;
+    m.n = n_steps;
+    m.beta = beta;
+    m.mt_key = h->rng_key;
+    m.mt_pos = h->rng_pos;
+    m.mask = h->mix_mask;
+    if (hipError_t e = gf::launch_mix_mask(m, h->stream); e != hipSuccess) return fail_hip("flock_mix_mask_kernel", e);
+  }
+  if (hipError_t e = gf::launch_policy_rollout(a, h->stream); e != hipSuccess)
+    return fail_hip("flock_policy_rollout_kernel launch", e);
+  return rollout_finish(h, bw, parts, dev, kParts, to_host);
 }
 
 // fe_step_host and fe_step_host_knn: knn_idx / knn_obs (either non-NULL) also rank the new

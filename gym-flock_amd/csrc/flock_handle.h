@@ -203,6 +203,17 @@ struct fe_handle {
   double* dt_steps = nullptr;                 // (dt_rows,B), grows on demand
   size_t dt_steps_cap = 0;                    // doubles allocated
   int dt_rows = 0;                            // rows the latest draw wrote (0: none yet)
+  // fe_set_policy / fe_step_policy: the learner's network as the kernel's LDS image, the
+  // taps 1 .. n_taps-1 of the current state's aggregation, and the per-step choices a call
+  // with 0 < beta < 1 draws (flock_dt_noise.hip)
+  bool has_policy = false;
+  gf::PolicyNet policy{};                     // (.image: pol_image)
+  float* pol_image = nullptr;                 // grow-only
+  size_t pol_image_cap = 0;                   // floats allocated
+  float* taps = nullptr;                      // (B,N,n_taps-1,6), grow-only
+  size_t taps_cap = 0;                        // floats allocated
+  uint8_t* mix_mask = nullptr;                // (n_steps,B), grows on demand
+  size_t mix_mask_cap = 0;
 };
 
 // capi.hip: each env's get_stats means into stats_sum. Internal like the calls below, but

@@ -241,6 +241,59 @@ struct RolloutArgs {
 int rollout_chunk_bits(int N);  // columns per pass-2 thread: 16, 32, 64 for N <= 64, 128, 256
 hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s);
 
+// The DAgger rollout (flock_policy_rollout.hip): the expert rollout's step, driven per step
+// by the expert or by a small per-agent network over delayed aggregation features.
+constexpr int kPolicyMaxTaps = 4, kPolicyMaxLayers = 3, kPolicyMaxWidth = 64;
+// The network as the kernel keeps it in LDS (float32). A hidden layer of n_in inputs and
+// w_out outputs gives each of a row's four threads Pw = w_out / 4 consecutive outputs,
+// padded to PS = 4 * ceil(Pw / 4) so that a thread reads its weights of one input as float4s:
+// weights [n_in][4][PS] (entry [i][q][m] = weight[q * Pw + m][i], 0 for m >= Pw), then the
+// biases [4][PS]. The last layer (2 outputs): weights [n_in][4] (entry [i][o], 0 for
+// o >= 2), then 4 biases.
+struct PolicyNet {
+  const float* image;     // device: the layers in the layout above, n_floats of them
+  int n_floats;
+  int n_layers, n_taps;
+  int width[kPolicyMaxLayers + 1];
+  int off_w[kPolicyMaxLayers], off_b[kPolicyMaxLayers];  // float offsets into image
+  float clip;             // > 0: the two outputs are clipped to [-clip, clip]
+};
+// Floats of the image of a network of these widths, and the offsets into it (any may be
+// nullptr); what the kernel reads past a layer's real outputs is zero-filled by the packer.
+int policy_image_floats(int n_layers, const int* width, int* off_w, int* off_b);
+// weight[l] (width[l+1], width[l]) row-major and bias[l] into `image` (policy_image_floats)
+void policy_pack_image(int n_layers, const int* width, const float* const* weight, const float* const* bias,
+                       float* image);
+struct PolicyRolloutArgs {
+  // As the expert rollout's (dt_steps unused). r.s.state_values is also read: tap 0 of the
+  // state before the first step.
+  RolloutArgs r;
+  PolicyNet net;
+  float* taps;            // (B,N,n_taps-1,6) taps 1.. of the state before the first step; the
+                          // last step writes the final state's (nullptr with n_taps == 1)
+  const uint8_t* mask;    // (n_steps,B) used_expert of every step, or nullptr: mask_const
+  int mask_const;
+  float* rec_agg;         // (K,B,N,n_taps,6)
+  float* rec_policy;      // (K,B,N,2)
+  double* rec_applied;    // (n_steps,B,N,2)
+  uint8_t* rec_used;      // (n_steps,B)
+};
+// The kernel's dynamic LDS: the one expression of the host's guard and of the launch.
+size_t policy_rollout_lds_bytes(int N, int n_taps, int image_floats);
+constexpr size_t kPolicyLdsMax = 80 * 1024;  // two workgroups per CU (160 KB)
+hipError_t launch_policy_rollout(const PolicyRolloutArgs& a, hipStream_t s);
+
+// flock_dt_noise.hip: n consecutive random_sample() doubles per env from the env's stream,
+// mask[t * B + b] = (the t-th of env b) < beta. The cached Gaussian is left alone.
+struct MixMaskArgs {
+  int B, n;
+  double beta;
+  uint32_t* mt_key;       // (B,624)
+  int32_t* mt_pos;        // (B) in [0, 624]
+  uint8_t* mask;          // (n,B) out
+};
+hipError_t launch_mix_mask(const MixMaskArgs& a, hipStream_t s);
+
 // Launch-geometry helpers shared by host and tests.
 int step_rows_per_block(int N);
 int step_tile(int N);

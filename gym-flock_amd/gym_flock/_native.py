@@ -71,6 +71,22 @@ class FeRollout(ctypes.Structure):
                 ("record_every", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
+FE_ACT_RELU = 0
+
+
+class FePolicy(ctypes.Structure):
+    _fields_ = [("weight", ctypes.c_void_p * 3), ("bias", ctypes.c_void_p * 3), ("clip", ctypes.c_double),
+                ("n_taps", ctypes.c_int32), ("n_layers", ctypes.c_int32), ("width", ctypes.c_int32 * 4),
+                ("activation", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class FePolicyRollout(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("state_values", ctypes.c_void_p), ("adj_bits", ctypes.c_void_p),
+                ("degree", ctypes.c_void_p), ("controls", ctypes.c_void_p), ("agg", ctypes.c_void_p),
+                ("policy", ctypes.c_void_p), ("applied", ctypes.c_void_p), ("used_expert", ctypes.c_void_p),
+                ("rewards", ctypes.c_void_p), ("record_every", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
 class CovRollout(ctypes.Structure):
     _fields_ = [("rewards", ctypes.c_void_p), ("done", ctypes.c_void_p), ("actions", ctypes.c_void_p),
                 ("needs_random", ctypes.c_void_p), ("flat_obs", ctypes.c_void_p),
@@ -246,6 +262,10 @@ SIGNATURES = {
     "fe_compute_helpers": [_P, _I],
     "fe_step": [_P, _P, _I],
     "fe_step_expert": [_P, _I, ctypes.POINTER(FeRollout)],
+    "fe_set_policy": [_P, ctypes.POINTER(FePolicy)],
+    "fe_reset_aggregation": [_P, _P],
+    "fe_get_aggregation": [_P, _I, _P],
+    "fe_step_policy": [_P, _I, ctypes.c_double, ctypes.POINTER(FePolicyRollout)],
     "fe_step_host": [_P, _P, _P, _P, _P, _P, _I],
     "fe_step_host_knn": [_P, _P, _P, _P, _P, _P, _P, _I],
     "fe_step_host_knn_ctrl": [_P, _P, _P, _P, _P, _P, _P, _P, _I],
@@ -589,6 +609,7 @@ class FlockHandle:
                             int(n_neighbors), int(device))
         self.n_agents, self.n_envs, self.n_neighbors = int(n_agents), int(n_envs), int(n_neighbors)
         self._dt_noise, self._dt_rows, self._dt_rows_max = False, 0, 1  # set_dt_noise / dt_steps
+        self.n_taps = 0  # set_policy: the taps of the policy set (0: none)
         h = ctypes.c_void_p()
         check(self.lib.fe_create(ctypes.byref(self.cfg), ctypes.byref(h)))
         self.h = h
@@ -878,6 +899,88 @@ class FlockHandle:
             out["dt"] = self.dt_steps()
         elif dt_addr is not None:
             self.dt_steps(device_ptr=dt_addr)
+        return out
+
+    # -- DAgger rollouts (include/gymflock.h fe_policy, fe_step_policy)
+    def set_policy(self, weights, biases, n_taps, clip=0.0):
+        """The learner of step_policy (fe_set_policy): weights[l] (width[l+1], width[l]) and
+        biases[l] (width[l+1]) of up to 3 linear layers (torch.nn.Linear's layout), cast to
+        float32, ReLU between them; the first layer reads 6 * n_taps inputs, the last gives 2
+        outputs. weights None removes the policy. The taps of all envs are zeroed."""
+        if weights is None:
+            check(self.lib.fe_set_policy(self.h, None))
+            self.n_taps = 0
+            return
+        w = [np.ascontiguousarray(a, dtype=np.float32) for a in weights]
+        b = [np.ascontiguousarray(a, dtype=np.float32) for a in biases]
+        if len(w) != len(b) or not 1 <= len(w) <= 3:
+            raise GymFlockError(GF_EINVAL, "set_policy: 1..3 layers, one bias per weight")
+        pol = FePolicy()
+        pol.n_taps, pol.n_layers, pol.clip, pol.activation = int(n_taps), len(w), float(clip), FE_ACT_RELU
+        for l, (wl, bl) in enumerate(zip(w, b)):
+            if wl.ndim != 2 or bl.shape != (wl.shape[0],) or (l > 0 and wl.shape[1] != w[l - 1].shape[0]):
+                raise GymFlockError(GF_EINVAL, "set_policy: layer %d: weight (out, in), bias (out), in = the layer "
+                                               "before's out" % l)
+            pol.weight[l], pol.bias[l] = wl.ctypes.data, bl.ctypes.data
+            pol.width[l], pol.width[l + 1] = wl.shape[1], wl.shape[0]
+        check(self.lib.fe_set_policy(self.h, ctypes.byref(pol)))
+        self.n_taps = int(n_taps)
+
+    def reset_aggregation(self, envs=None):
+        """Zero the taps k >= 1 of the selected envs (None: all; a bool mask or an index
+        list), fe_reset_aggregation."""
+        mask = None
+        if envs is not None:
+            e = np.asarray(envs)
+            if e.dtype == np.bool_:
+                assert e.shape == (self.n_envs,), e.shape
+                mask = np.ascontiguousarray(e, dtype=np.uint8)
+            else:
+                mask = np.zeros(self.n_envs, np.uint8)
+                mask[e.astype(np.int64)] = 1
+        check(self.lib.fe_reset_aggregation(self.h, ptr(mask)))
+
+    def aggregation(self, env=None):
+        """z of the current state, (B,N,n_taps,6) float32 or (N,n_taps,6) of one env
+        (fe_get_aggregation)."""
+        k = max(self.n_taps, 1)
+        shape = (self.n_agents, k, 6) if env is not None else (self.n_envs, self.n_agents, k, 6)
+        out = np.empty(shape, np.float32)
+        check(self.lib.fe_get_aggregation(self.h, -1 if env is None else int(env), ptr(out)))
+        return out
+
+    def policy_shapes(self, n_steps, every=1):
+        """name -> (shape, dtype) of fe_step_policy's records (fe_policy_rollout)."""
+        k, b, n = n_steps // every, self.n_envs, self.n_agents
+        shapes = self.rollout_shapes(n_steps, every)
+        shapes.update({"agg": ((k, b, n, max(self.n_taps, 1), 6), np.float32),
+                       "policy": ((k, b, n, 2), np.float32), "applied": ((n_steps, b, n, 2), np.float64),
+                       "used_expert": ((n_steps, b), np.uint8)})
+        return shapes
+
+    def step_policy(self, n_steps, beta=0.0, record=(), every=1, fetch=True, device_ptrs=None):
+        """n_steps of the DAgger loop in one launch (fe_step_policy): each step applies the
+        expert's action with probability beta, else the policy's. record / every / fetch /
+        device_ptrs as step_expert, names and shapes in policy_shapes()."""
+        n_steps, every = int(n_steps), int(every)
+        shapes = self.policy_shapes(max(n_steps, 0), max(every, 1))
+        rec = FePolicyRollout()
+        rec.record_every = every
+        out = None
+        if device_ptrs is not None:
+            for name, addr in device_ptrs.items():
+                if name not in shapes:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+                setattr(rec, name, ctypes.c_void_p(int(addr)))
+            rec.flags = FE_ROLLOUT_DEVICE
+        elif fetch:
+            out = {}
+            for name in record:
+                if name not in shapes:
+                    raise ValueError("unknown record %r (one of %s)" % (name, ", ".join(sorted(shapes))))
+                out[name] = np.empty(*shapes[name])
+                setattr(rec, name, out[name].ctypes.data_as(ctypes.c_void_p))
+        check(self.lib.fe_step_policy(self.h, n_steps, float(beta), ctypes.byref(rec)))
         return out
 
     def step_host(self, u_addr, f64, sv, net, rew, ctrl):

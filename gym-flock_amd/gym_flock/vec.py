@@ -54,6 +54,8 @@ class VecFlockingRelative:
             x = synthetic_batch(self.n_envs, self.n_agents, seed + self.env_offset, self.v_max)
         self.h.set_state(x)
         self.h.compute_helpers()
+        if self.h.n_taps:  # a policy is set (set_policy here or on the handle)
+            self.h.reset_aggregation()
         return x
 
     def reset_device(self, seed=None, envs=None, reject=True, max_tries=4096, r_max=None, fetch=True,
@@ -77,6 +79,8 @@ class VecFlockingRelative:
         s = None if seed is None else int(seed) + self.env_offset
         out = self.h.reset_device(s, envs, reject, max_tries, r_max, self.v_max, fetch=fetch, kind=kind)
         self.h.compute_helpers()
+        if self.h.n_taps:  # a policy is set (set_policy here or on the handle)
+            self.h.reset_aggregation(envs)
         return out
 
     def np_random(self, env):
@@ -146,6 +150,39 @@ class VecFlockingRelative:
         are the last step's; network() raises until compute_helpers() or a step that
         writes the dense network."""
         return self.h.step_expert(n_steps, record, every, fetch, device_ptrs)
+
+    def set_policy(self, weights, biases, n_taps, clip=0.0):
+        """The learner of policy_steps: one network shared by all agents over n_taps (1..4)
+        delayed aggregation taps of 6 features each (tap 0 the state_values, tap k the
+        neighbourhood mean, or sum without mean_pooling, of the previous state's tap k - 1;
+        zero at an episode's start). weights / biases: lists of up to 3 arrays in
+        torch.nn.Linear's layout ((out, in) and (out)), cast to float32; 6 * n_taps inputs,
+        hidden widths multiples of 4 up to 64, 2 outputs, ReLU between layers; clip > 0
+        clips the outputs to [-clip, clip]. weights=None removes it. Zeroes every env's taps."""
+        self.h.set_policy(weights, biases, n_taps, clip)
+
+    def policy_steps(self, n_steps, beta=0.0, record=("rewards",), every=1, fetch=True, device_ptrs=None):
+        """n_steps of the DAgger loop for every env in ONE launch (fe_step_policy, n_agents <=
+        256, FlockingRelative only): each step integrates the expert's action with
+        probability beta (one random_sample() of the env's device stream per step, the
+        stream of reset_device; beta 0 and 1 draw nothing), else the policy's action for the
+        current aggregation; the expert's action of every state reached is recorded as
+        the label. Needs set_policy and a controller output of the current state.
+        record: expert_steps' names, and "agg" (K,B,N,n_taps,6) float32, "policy"
+        (K,B,N,2) float32 (the learner's action for the recorded state), "applied"
+        (n_steps,B,N,2) (what each step integrated) and "used_expert" (n_steps,B) uint8.
+        (agg, controls) of a record is one DAgger pair. every / fetch / device_ptrs and the
+        getters afterwards as expert_steps; aggregation() is the final state's."""
+        return self.h.step_policy(n_steps, beta, record, every, fetch, device_ptrs)
+
+    def aggregation(self, env=None):
+        """The current state's aggregation features (B,N,n_taps,6) float32, or one env's."""
+        return self.h.aggregation(env)
+
+    def reset_aggregation(self, envs=None):
+        """Zero the taps k >= 1 of the envs (None: all): an episode's start. reset() and
+        reset_device() do it for the envs they touch; after set_state() it is the caller's."""
+        self.h.reset_aggregation(envs)
 
     def compute_helpers(self):
         """compute_helpers() on the current state: every observation buffer anew."""

@@ -261,6 +261,73 @@ typedef struct fe_rollout {
  * ranks the final state anew. Closed-loop stepping, or another rollout, goes on without a
  * new fe_controller. */
 int fe_step_expert(fe_handle* h, int n_steps, const fe_rollout* rec /* or NULL */);
+
+/* DAgger rollouts (FlockingRelative-v0, n_agents <= 256): fe_step_expert's loop in which a
+ * learner drives with probability 1 - beta per step and env, and the expert labels every
+ * state the loop reaches.
+ *
+ * The learner is one network shared by all agents over delayed aggregation features
+ * z_t (N, n_taps, 6) float32 (Tolstaya et al., CoRL 2020, in recursive form):
+ *   z_t[i,0,:] = state_values_t[i,:]
+ *   z_t[i,k,:] = float32((sum over j adjacent to i in state t of double(z_{t-1}[j,k-1,:])) / d_i), k >= 1,
+ * d_i = max(degree_t[i], 1) with mean_pooling, else 1; every tap k >= 1 is zero at an
+ * episode's start. Taps 1 .. n_taps-1 of the current state are kept on the handle.
+ * Network: n_layers linear layers of widths width[0] = 6 * n_taps, ..., width[n_layers] = 2,
+ * hidden widths multiples of 4 and at most 64; weight[l] (width[l+1], width[l]) row-major
+ * (torch.nn.Linear.weight), bias[l] (width[l+1]); ReLU (x > 0 ? x : 0) after every layer but
+ * the last. All of it float32, in one fixed order: the input is z_t[i] flattened (index
+ * 6k + f); an output starts from its bias and adds weight[o][i] * x[i] for i ascending,
+ * every product and every sum rounded once (no fused multiply-add). clip > 0 (rounded to
+ * float32): both outputs clipped to [-clip, clip]. The action applied is double(output). */
+#define FE_ACT_RELU 0
+typedef struct fe_policy {
+  const float* weight[3]; /* host pointers, copied by the call */
+  const float* bias[3];
+  double  clip;           /* 0: none */
+  int32_t n_taps;         /* 1..4 */
+  int32_t n_layers;       /* 1..3 */
+  int32_t width[4];
+  int32_t activation;     /* FE_ACT_RELU */
+  int32_t reserved;
+} fe_policy;              /* 88 bytes */
+/* NULL removes the policy. Either way the taps of all envs are zeroed. */
+int fe_set_policy(fe_handle* h, const fe_policy* policy);
+/* Zero the taps k >= 1 of the selected envs (env_mask (B), or NULL: all). The taps advance
+ * only in fe_step_policy: a caller that resets envs or sets their state calls this for them,
+ * as a caller that sets state calls fe_compute_helpers. GF_ESTATE without a policy. */
+int fe_reset_aggregation(fe_handle* h, const uint8_t* env_mask);
+/* z of the current state: dst (B,N,n_taps,6), or (N,n_taps,6) of env >= 0. */
+int fe_get_aggregation(fe_handle* h, int env /* -1 = all */, float* dst);
+
+/* Records of fe_step_policy: fe_rollout's, of the state after the step (K = n_steps /
+ * record_every of them), and the loop's own. (agg, controls) of a record is one DAgger
+ * pair. Every pointer may be NULL. */
+typedef struct fe_policy_rollout {
+  double*   x;            /* as fe_rollout */
+  float*    state_values;
+  uint64_t* adj_bits;
+  int32_t*  degree;
+  double*   controls;
+  float*    agg;          /* (K,B,N,n_taps,6) z of the recorded state                */
+  float*    policy;       /* (K,B,N,2) the learner's action for the recorded state   */
+  double*   applied;      /* (n_steps,B,N,2) the action each step integrated         */
+  uint8_t*  used_expert;  /* (n_steps,B) 1: that step applied the expert's action    */
+  double*   rewards;      /* (n_steps,B)                                             */
+  int32_t   record_every;
+  int32_t   flags;        /* FE_ROLLOUT_DEVICE */
+} fe_policy_rollout;      /* 88 bytes */
+/* n_steps of: applied = used_expert ? controller() : policy(z); step(applied); then the new
+ * state's observation, controller(), z and policy(z). used_expert[t,b] = (u < beta), u one
+ * random_sample() double of env b's stream per step (the stream fe_reset_device seeds and
+ * continues; all n_steps doubles are drawn by one launch ahead of the rollout; the cached
+ * Gaussian is not touched); beta 0 and 1 draw nothing and need no stream.
+ * Stream order, staging and the handle's state afterwards are fe_step_expert's; the taps on
+ * the handle are the final state's.
+ * GF_EINVAL: n_steps < 1, beta outside [0,1] or NaN, record_every < 1 or not dividing
+ * n_steps, unknown flags, n_agents > 256, a handle with a variant, a per-env dt or
+ * fe_set_dt_noise. GF_ESTATE: no policy, no controller output of the current state,
+ * 0 < beta < 1 with a stream never seeded or set, a handle with a communicator. */
+int fe_step_policy(fe_handle* h, int n_steps, double beta, const fe_policy_rollout* rec /* or NULL */);
 /* The drop-in env's step(u) (:91-109) as one launch and one wait, for small batches
  * where latency, not bandwidth, counts (FlockingRelativeEnv.step, N ~ 100-1000, B = 1).
  * u: (B,N,2) host actions, float32 or float64 (FE_U_F64). One env of at most one tile
